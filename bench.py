@@ -7,9 +7,12 @@
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0).  `value` = images/sec over all ranks with inputs resident in HBM;
-`roofline` = the dominant kernel family timed with HIP events on its own stream (libnkbhip profiler);
-`cpu_baseline` = the CPU oracle (torch fp32 restatement of the reference path) timed on a bounded sample.
+Prints ONE JSON line (rank 0).  `value` = images/sec over all ranks with inputs resident in HBM.  A plain run sets up,
+warms up, times the steps and prints the line; `--full` adds the measurements the headline does not need, each after the
+timed region: `host_work_ms_per_step` (batch-4 steps), `roofline` / `kernel_ms_per_step` (the dominant kernel family timed
+with HIP events on its own stream, libnkbhip profiler) and `cpu_baseline` (the CPU oracle, a torch fp32 restatement of the
+reference path, timed on a bounded sample).  `--dump-outputs DIR` writes what the last timed step returned (loss, logits, the
+logger's softmax / argmax) and a seeded sample of the parameters, gradients and buffers it left, as float32 DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -128,12 +131,20 @@ def parse():
                          "DeviceLoader (async H2D one batch ahead + on-GPU pad/flip/normalise). host-fp32: the reference's "
                          "way, a blocking fp32 .to(device) per step (engine.py:40).  The host variants are PCIe-inclusive "
                          "rates for DESIGN.md, never the headline.")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure host work at batch 4, the per-kernel roofline and the CPU baseline "
+                         "(each can be left out again with the --no-* option below)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-host-work", action="store_true", help="skip the batch-4 host-work measurement (profiler runs)")
     ap.add_argument("--cpu-batch", type=int, default=16)
     ap.add_argument("--cpu-steps", type=int, default=5)       # >= 5 timed steps
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as float32 DIR/<name>.npy (at most 64 MB in all)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def build(args, device):
@@ -248,6 +259,26 @@ def cpu_baseline(args):
     return out
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """Writes `arrays` (name -> tensor) as float32 <directory>/<name>.npy.  An array above its equal share of DUMP_BYTES is
+    replaced by a sample of its flattened elements at seeded, sorted positions, so two builds given the same arguments write
+    the same elements."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    cap = DUMP_BYTES // 4 // len(arrays)
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > cap:
+            flat = t.reshape(-1)
+            idx = torch.randint(flat.numel(), (cap,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = flat[idx.to(flat.device)]
+        np.save(os.path.join(directory, f"{name}.npy"), t.float().cpu().numpy())
+    log(f"outputs of the last timed step written to {directory}: {', '.join(arrays)}")
+
+
 def main():
     args = parse()
     # stdout carries exactly ONE line, the JSON: native libraries (the RCCL version banner, NCCL_DEBUG output) write to file
@@ -335,9 +366,9 @@ def main():
             loss = loss["loss"]     # MultitaskCriterion: per-task losses + their sum (losses.py:97-151)
         loss.backward()
         opt.step()
-        for p_ in (preds.values() if heads else (preds,)):
-            softmax_argmax(p_)      # the logger's per-step by-products (device side, no host sync)
-        return loss
+        # the logger's per-step by-products (device side, no host sync)
+        side = [softmax_argmax(p_) for p_ in (preds.values() if heads else (preds,))]
+        return loss, preds, side
 
     # first step packs the arena; broadcast rank-0 state afterwards so all ranks start identical
     log("model built; first step")
@@ -370,7 +401,7 @@ def main():
     t0 = time.perf_counter()
     step_marks = []
     for _ in range(args.steps):
-        loss = step()
+        loss, preds, side = step()
         step_marks.append(time.perf_counter())
     host_dt = time.perf_counter() - t0          # time to ENQUEUE the steps (host side only)
     torch.cuda.synchronize()
@@ -397,12 +428,22 @@ def main():
             dist.destroy_process_group()
         raise SystemExit(f"bench.py: non-finite loss (this rank: {final_loss}) after the timed steps; refusing to report a throughput")
     log(f"timed region: {dt:.3f}s for {args.steps} steps")
+    if rank == 0 and args.dump_outputs:
+        arrays = {"loss": loss}
+        for (name, p_), (probs, am) in zip(preds.items() if heads else [("", preds)], side):
+            sfx = f"_{name}" if name else ""
+            arrays.update({f"logits{sfx}": p_, f"probs{sfx}": probs, f"argmax{sfx}": am})
+        arrays.update(params=model.arena.flat_param, grads=model.arena.flat_grad)
+        bufs = [b.reshape(-1).float() for b in model.buffers() if b.is_floating_point()]
+        if bufs:
+            arrays["buffers"] = torch.cat(bufs)      # BatchNorm running statistics
+        dump_outputs(args.dump_outputs, arrays)
 
     # host work per step: the enqueue loop above runs ahead until the HIP queue throttles it, so host_enqueue_ms_per_step is
     # queue back-pressure, not work.  The work itself is independent of the batch (same launches): time it at batch 4, where
     # the GPU finishes each step long before the host has enqueued the next.
     host_work = None
-    if rank == 0 and args.input == "hbm" and world == 1 and not force_dist and not args.no_host_work:
+    if args.full and rank == 0 and args.input == "hbm" and world == 1 and not force_dist and not args.no_host_work:
         small_x = img[:4].clone()
         small_t = {k: v[:4].clone() for k, v in tgt.items()} if heads else tgt[:4].clone()
         keep = (img, tgt)
@@ -431,12 +472,13 @@ def main():
     feed = None
     roofline = None
     prof = {}
-    if not args.no_roofline and rank != 0:
+    roofline_leg = args.full and not args.no_roofline
+    if roofline_leg and rank != 0:
         # the profiled steps below exchange gradients like any other step, so every rank takes them; only rank 0 profiles
         for _ in range(min(args.steps, 5)):
             step()
         torch.cuda.synchronize()
-    if rank == 0 and not args.no_roofline:
+    if rank == 0 and roofline_leg:
         # same step, re-run with one HIP-event pair per launch on the launch stream (perturbs wall time, so it is
         # kept out of the timed region above)
         nprof = min(args.steps, 5)
@@ -492,7 +534,7 @@ def main():
         dist.barrier()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args)
 
     if rank == 0:

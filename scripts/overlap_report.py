@@ -1,6 +1,6 @@
-"""Where the wall time of an OVERLAPPED train step goes (rocprofv3 kernel-trace CSV of bench.py).
+"""Where the wall time of an OVERLAPPED train step goes (rocprofv3 kernel-trace CSV of bench.py --full).
 
-bench.py's timed steps run the weight gradients on a side stream; its last 5 steps are serialized for the roofline events.  This
+bench.py --full: the timed steps run the weight gradients on a side stream; its last 5 steps are serialized for the roofline events.  This
 script takes the overlapped steps just before those and reports, per step: wall span, per-queue busy time, time during which NO
 kernel was running (launch gaps / dependency bubbles), time with >= 2 kernels running, and per kernel family the average duration
 in the overlapped steps next to the serialized ones (the stretch is what co-running costs that kernel).

@@ -1,4 +1,4 @@
-"""Per-kernel summary of the LAST `keep` train steps in a rocprofv3 kernel-trace CSV (bench.py runs its HIP-event
+"""Per-kernel summary of the LAST `keep` train steps in a rocprofv3 kernel-trace CSV (bench.py --full runs its HIP-event
 profiled steps last, with the weight-gradient stream folded onto the main stream, so these are the launches the
 `roofline` object of the bench line is computed from).  Step boundaries = launches of optim_step_kernel.
 Usage: python scripts/profile_summary.py <kernel_trace.csv> <keep> <out.csv>"""
