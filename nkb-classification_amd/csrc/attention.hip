@@ -375,6 +375,7 @@ __global__ __launch_bounds__(NKB_ATTN_BWD_THREADS, 1) void attn_bwd_fused_kernel
     // row sums of dO o O went through 8 LDS float atomics per row): every global load is issued first, delta is reduced over the 8
     // lanes that hold a row's chunks by DPP (a fixed order — the atomics' was not) and stored once.
     static_assert(ROWS <= NT, "one lse row per thread");
+    static_assert((ROWS * 8) % 64 == 0, "the row loop below breaks out in whole waves: the DPP reduction needs all 8 lanes of a row");
     {
         u32x4 rq[IT], rk[IT], rv[IT], rd[IT], ro[IT];
         float lv = 0.f;
