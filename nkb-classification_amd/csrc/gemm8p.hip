@@ -29,6 +29,9 @@
 #include "gemm8p.h"
 #include <type_traits>
 #include <atomic>
+#include <map>
+#include <mutex>
+#include <utility>
 
 #ifdef NKB_G8_STAMPS
 // diagnostic build only (scripts/g8_stamps.py): s_memtime of wave 0 / wave 4 of every workgroup at the top of a tile's first four
@@ -1007,7 +1010,7 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const G8Params p) {
 // ---------------------------------------------------------------------------------------------------------------------
 // The RAGGED ROWS of a persistent launch as their own small kernel (round 5).  When M is no multiple of 256 the last row block's
 // tiles cost a whole tile time each — and where they are what pushes the tile count over a multiple of the CU count they cost
-// the launch a whole ROUND: unicom ViT-L/14 at batch 128 has M = 32 896 = 128.5 x 256, so each of its N = 1 024 launches walks
+// the launch a whole ROUND: a 257-token ViT-L at batch 128 has M = 32 896 = 128.5 x 256, so each of its N = 1 024 launches walks
 // 516 = 2 x 256 + 4 tiles in three rounds (84 us against 62 for M = 32 768 at K = N = 1 024, 266 against 206 at K = 4 096).
 // nkb_launch_gemm8p then gives the persistent kernel the whole row blocks only and these R = M % 256 rows to this kernel:
 // grid = (N / 64 column blocks) x S splits of K, 8 waves; four of them multiply its R x 64 x (K / S) piece straight from global
@@ -1015,9 +1018,9 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const G8Params p) {
 // ticket; the block's LAST arriver adds the S slabs in split order — the same sum whoever arrives last — and applies the epilogue of
 // gemm8p's `value()` (bias, residual, saved-derivative multiply / ReLU6 mask, ReLU / ReLU6 / GELU + GELU').  Hand-off as in
 // elementwise.hip (write-through stores, vmcnt(0), barrier, agent-scope ticket, the last arriver clears it and acquires once).
-constexpr int G8R_SLOTS = 2, G8R_MAXWG = 768, G8R_COLS = 64;
-__device__ float g8r_slabs[G8R_SLOTS * G8R_MAXWG * 256 * G8R_COLS / 2];   // R <= 128 per [split][block] piece in the common case; sized for R = 128
-__device__ unsigned g8r_tickets[G8R_SLOTS * 128];
+// The slabs and tickets are scratch of the launching STREAM (g8r_scratch): launches on one stream run one after the other and
+// reuse them; launches on two streams may run at the same time and never share them.
+constexpr int G8R_MAXWG = 768, G8R_COLS = 64;
 
 struct G8RParams {
     const bf16_t* x; const bf16_t* w; bf16_t* y; bf16_t* y2;
@@ -1255,6 +1258,34 @@ static int g8_rounds(int tiles, int cus) { return (tiles + cus - 1) / cus; }
 static int g8_ragged_on = NKB_G8_RAGGED;
 // run-time switch (tests, A/B timing): 1 = the ragged rows of a persistent launch go to gemm8p_ragged_kernel where that saves a round
 extern "C" void nkb_gemm8p_ragged(int on) { g8_ragged_on = on; }
+// The companion's scratch on `stream` (of the current device): >= `floats` fp32 slab floats and 128 tickets, all zero before first
+// use (the last arriver of a column block clears its ticket again).  Allocated on the first ragged launch of a stream and grown
+// when a launch needs more; the old slabs are freed only once the stream has finished with them.  false: allocation failed.
+static bool g8r_scratch(hipStream_t stream, size_t floats, float** slabs, unsigned** tickets) {
+    struct Scratch { float* slabs = nullptr; unsigned* tickets = nullptr; size_t floats = 0; };
+    static std::mutex mu;
+    static std::map<std::pair<int, hipStream_t>, Scratch> per_stream;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return false;
+    std::lock_guard<std::mutex> lock(mu);
+    Scratch& sc = per_stream[{dev, stream}];
+    if (!sc.tickets) {
+        if (hipMalloc((void**)&sc.tickets, 128 * sizeof(unsigned)) != hipSuccess) { sc.tickets = nullptr; return false; }
+        if (hipMemsetAsync(sc.tickets, 0, 128 * sizeof(unsigned), stream) != hipSuccess) return false;
+    }
+    if (sc.floats < floats) {
+        if (sc.slabs) {
+            if (hipStreamSynchronize(stream) != hipSuccess) return false;   // (its earlier launches may still read the old slabs)
+            (void)hipFree(sc.slabs);
+            sc.slabs = nullptr; sc.floats = 0;
+        }
+        if (hipMalloc((void**)&sc.slabs, floats * sizeof(float)) != hipSuccess) { sc.slabs = nullptr; return false; }
+        sc.floats = floats;
+    }
+    *slabs = sc.slabs; *tickets = sc.tickets;
+    return true;
+}
+
 // Launches the companion for rows [M0, M0 + R) of the problem in `p` (pointers of the FULL problem); false: shape not served.
 static bool g8_launch_ragged(const G8Params& p, int M0, int R, hipStream_t stream) {
     if (R < 1 || R > 128 || p.N % G8R_COLS != 0 || p.row_scale || p.yq || p.mask_in || p.mask_out || p.colpart || p.stats) return false;
@@ -1266,19 +1297,17 @@ static bool g8_launch_ragged(const G8Params& p, int M0, int R, hipStream_t strea
     const int deep = p.K >= 2048 ? 256 : 128;
     for (int c = 2; c <= 16; ++c)
         if (p.K % (32 * c) == 0 && p.K / c >= deep && blocks * c <= G8R_MAXWG) S = c;
-    static std::atomic<unsigned> turn{0};
+    const int RF = R <= 64 ? 1 : 2;
     float* slabs = nullptr; unsigned* tickets = nullptr;
-    if (hipGetSymbolAddress((void**)&slabs, HIP_SYMBOL(g8r_slabs)) != hipSuccess || hipGetSymbolAddress((void**)&tickets, HIP_SYMBOL(g8r_tickets)) != hipSuccess ||
-        !slabs || !tickets)
-        return false;
-    const unsigned slot = turn.fetch_add(1u) % G8R_SLOTS;
+    if (!g8r_scratch(stream, (size_t)blocks * S * (4 * RF * 4 * 256), &slabs, &tickets)) return false;
     G8RParams q;
     q.x = p.x + (size_t)M0 * p.ldx; q.w = p.w; q.y = p.y + (size_t)M0 * p.ldy; q.y2 = p.y2 ? p.y2 + (size_t)M0 * p.ldy : nullptr;
     q.bias = p.bias; q.add = p.add ? p.add + (size_t)M0 * p.ldadd : nullptr; q.aux = p.aux ? p.aux + (size_t)M0 * p.ldy : nullptr;
     q.R = R; q.N = p.N; q.K = p.K; q.ldx = p.ldx; q.ldw = p.ldw; q.ldy = p.ldy; q.ldadd = p.ldadd; q.relu = p.relu;
     q.aux_kind = p.aux ? 1 + p.aux_mode : 0; q.S = S;
-    q.slab = slabs + (size_t)slot * G8R_MAXWG * 128 * G8R_COLS; q.ticket = tickets + slot * 128;
+    q.slab = slabs; q.ticket = tickets;
     const dim3 grid((unsigned)blocks, (unsigned)S);
+    nkb_count_launch(11);
     if (R <= 64) hipLaunchKernelGGL(gemm8p_ragged_kernel<1>, grid, dim3(512), 0, stream, q);
     else hipLaunchKernelGGL(gemm8p_ragged_kernel<2>, grid, dim3(512), 0, stream, q);
     return true;
@@ -1383,6 +1412,7 @@ extern "C" int nkb_gemm_fp8(int mode, const void* xq, const void* wq, void* y, c
     NkbProfScope prof(mode == 0 ? NKB_K_CONV_FWD : NKB_K_CONV_DGRAD, stream, 2.0 * M * (double)N * K);
     p.stagger = g8_stagger(tiles, cus, K / 128);
     const dim3 grid((unsigned)g8_grid(tiles, cus));
+    nkb_count_launch(12);
     if (yq) {
         if (mode == 0) hipLaunchKernelGGL((gemm8p_kernel<true, 1, true>), grid, dim3(512), lds, stream, p);
         else hipLaunchKernelGGL((gemm8p_kernel<true, 2, true>), grid, dim3(512), lds, stream, p);
