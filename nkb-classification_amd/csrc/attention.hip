@@ -676,6 +676,6 @@ extern "C" int nkb_attn_backward(int dtype, const void* qkv, const void* dout, c
     }
 #undef NKB_ATTN_BWDF
     int rc = nkb_check_launch("attn_backward");
-    if (!rc && colsum) rc = nkb_launch_wgrad_reduce(colsum_work, 3ll * H * DH, B, colsum, 3ll * H * DH, stream);
+    if (!rc && colsum) rc = nkb_launch_wgrad_reduce(colsum_work, 3ll * H * DH, B, colsum, 3ll * H * DH, /*assign=*/false, stream);
     return rc;
 }

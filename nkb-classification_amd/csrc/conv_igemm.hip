@@ -28,10 +28,19 @@ template <> struct MmaTraits<float> { static constexpr int KSTEPS = 8; };   // 8
 
 __device__ __forceinline__ int lds_swz(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 
-// BNB: 0 plain epilogue; 1 fused BN-backward reduction with the ReLU mask recomputed from c (interior stages);
-//      2 the same for a stage that closes a residual block: mask from its bit array, residual operand still added
-//      3 plain bf16 epilogue only (bias / ReLU / per-tile statistics; no residual operand, activation epilogue, row
-//        remap or fp32 output): a lean row loop, selected by launch_conv when the launch qualifies
+// BNB, the epilogue selector (an int, so that the kernels' mangled names stay what profiles and scripts match on):
+//   EPI_GENERAL       every plain epilogue: bias, residual operand, ReLU / GELU-family activations, statistics, fp32 output, row remap
+//   EPI_BN_MASK       fused BN-backward reduction with the ReLU mask recomputed from c (interior stages); K-concatenated input allowed
+//   EPI_BN_BITS       the same for a stage that closes a residual block: mask from its bit array, residual operand still added
+//   EPI_LEAN          bf16, bias / ReLU / per-tile statistics / plain full-grid residual only (no activation epilogue, row remap
+//                     or fp32 output): a lean row loop, taken instead of EPI_GENERAL when the launch qualifies (lean_epilogue_ok)
+//   EPI_AFFINE_BITS   closing stage with the statistics known up front: relu(acc * oscale + bias + add') plus its ReLU bit mask;
+//                     K-concatenated input allowed
+//   EPI_BN_BITS_LEAN  bf16 EPI_BN_BITS for the common geometry (full-grid residual, 8-channel-aligned rows)
+//   EPI_BN_MASK_LEAN  bf16 EPI_BN_MASK for the common geometry (no residual, no parity-class remap)
+//   EPI_LEAN_CAT      EPI_LEAN's row loop over a K-concatenated input (nkb_conv_cat_bias)
+constexpr int EPI_GENERAL = 0, EPI_BN_MASK = 1, EPI_BN_BITS = 2, EPI_LEAN = 3, EPI_AFFINE_BITS = 4, EPI_BN_BITS_LEAN = 6,
+              EPI_BN_MASK_LEAN = 7, EPI_LEAN_CAT = 8;
 // HALO (bf16, 3x3 / stride 1 / pad 1, forward or data gradient): the three taps of one filter row share ONE staged
 //      activation tile of TP + 2 pixel rows (flattened pixels m0-1 .. m0+TP); tap s reads it shifted by s rows, and the
 //      lanes whose left / right neighbour lies in another image row get zeros.  Activation loads per channel chunk drop
@@ -378,7 +387,7 @@ __global__ __launch_bounds__(256, ((BNB && TC == 128) || TC == 64) ? 3 : 1) void
     // a load above a store through an unrelated pointer) and every row exposed two memory latencies (3.9 TB/s on three large tensors
     // where the closing-stage forward epilogue, same traffic shape, streams at 5+).
     constexpr bool F2 = BNB == 6 && sizeof(T) == 2;    // (its own instantiation: compiled next to the general loop it spilled 70 VGPRs)
-    constexpr bool fast2 = F2;                       // (launch_conv_closing only picks BNB == 6 when the geometry qualifies)
+    constexpr bool fast2 = F2;                       // (lean_epilogue_ok: BNB == 6 is only picked when the geometry qualifies)
     u32x4 apre2[F2 ? RPH : 1];
     unsigned abit2[F2 ? RPH : 1], obit2[F2 ? RPH : 1];
     auto prefetch_fast = [&](int half) {
@@ -842,23 +851,23 @@ __global__ __launch_bounds__(256, ((BNB && TC == 128) || TC == 64) ? 3 : 1) void
 // Weight gradient: dW[cout][n] += sum_m dY[m][cout] * X[src(m, tap(n))][cin(n)],  n = (r,s,cin) flattened.
 // Both operands are pixel-major, so MFMA fragments come from LDS through the transposing read
 // (ds_read_b64_tr_b16) for bf16 and through plain ds_read_b32 for fp32.
-struct WgradParams {
-    const void* dy;   // [M][lddy]
-    const void* x;    // [N][H][W][ldx]
-    float* dw;        // [Cout][R*S*Cin] fp32, accumulated with atomics
-    float* dbias;     // optional [Cout]: column sums of dY (accumulated with atomics by tile_n == 0)
-    int M, H, W, Cin, ldx;
-    int P, Q, Cout, lddy;
-    int R, S, stride, pad;
-    int stride_w, pad_w;   // horizontal stride / padding (== stride / pad except for the packed stem)
-    int Ntot;         // R*S*Cin
-    int tilesC, tilesN, splits, rows_per_split;
-    FastDiv divPQ, divQ, divCin, divS;
+struct WgradParams {   // (every field has a default: a caller writes what its launch uses)
+    const void* dy = nullptr;   // [M][lddy]
+    const void* x = nullptr;    // [N][H][W][ldx]
+    float* dw = nullptr;        // [Cout][R*S*Cin] fp32, accumulated with atomics
+    float* dbias = nullptr;     // optional [Cout]: column sums of dY (accumulated with atomics by tile_n == 0)
+    int M = 0, H = 0, W = 0, Cin = 0, ldx = 0;
+    int P = 0, Q = 0, Cout = 0, lddy = 0;
+    int R = 1, S = 1, stride = 1, pad = 0;
+    int stride_w = 1, pad_w = 0;   // horizontal stride / padding (== stride / pad except for the packed stem)
+    int Ntot = 0;     // R*S*Cin
+    int tilesC = 0, tilesN = 0, splits = 1, rows_per_split = 0;
+    FastDiv divPQ = {}, divQ = {}, divCin = {}, divS = {};
     // batched / direct-store form (attention dV, dK): blockIdx.z = zo*inner + zi; when out_t is set the single split
     // stores its tile in the compute dtype at out_t[z-offset + cout*ldo + n] instead of adding to dw
-    void* out_t;
-    int ldo, inner;
-    long long sdo, sdi, sxo, sxi, soo, soi;
+    void* out_t = nullptr;
+    int ldo = 0, inner = 1;
+    long long sdo = 0, sdi = 0, sxo = 0, sxi = 0, soo = 0, soi = 0;
     // deterministic form: every (tile, split) workgroup stores its fp32 tile into its own slab part[split][Cout][Ntot]
     // (plain stores, no atomics) and wgrad_reduce_kernel adds the slabs to dw in split order; bias partial sums go to
     // bpart[split * tilesN + tile_n][Cout]
@@ -1154,15 +1163,21 @@ __global__ void wgrad_reduce_scalar_kernel(const float* __restrict__ part, long 
         dst[i] = assign ? a : dst[i] + a;
     }
 }
-// nkb_conv_wgrad_assign: the reductions launched inside it OVERWRITE their destination (a scratch product such as the Gram-form R =
-// g^T a needs no memset in front of it).  Host-side flag of the calling thread; launches are enqueued synchronously inside the call.
-static thread_local bool g_wgrad_assign = false;
-int nkb_launch_wgrad_reduce(const float* part, long long slab, int splits, float* dst, long long n, hipStream_t stream) {
+template <bool ASSIGN>
+static void launch_wgrad_reduce_kernel(int sg, unsigned grid, hipStream_t stream, const float* part, long long slab, int splits, float* dst,
+                                       long long n, const float* part2, long long slab2, float* dst2, long long n2) {
+    if (sg == 16) hipLaunchKernelGGL((wgrad_reduce_kernel<16, ASSIGN>), dim3(grid), dim3(256), 0, stream, part, slab, splits, dst, n, part2, slab2, dst2, n2);
+    else if (sg == 4) hipLaunchKernelGGL((wgrad_reduce_kernel<4, ASSIGN>), dim3(grid), dim3(256), 0, stream, part, slab, splits, dst, n, part2, slab2, dst2, n2);
+    else hipLaunchKernelGGL((wgrad_reduce_kernel<1, ASSIGN>), dim3(grid), dim3(256), 0, stream, part, slab, splits, dst, n, part2, slab2, dst2, n2);
+}
+// assign: the reduction OVERWRITES its destination instead of adding to it (a scratch product such as the Gram-form R = g^T a needs
+// no memset in front of it)
+int nkb_launch_wgrad_reduce(const float* part, long long slab, int splits, float* dst, long long n, bool assign, hipStream_t stream) {
     if (n <= 0 || splits <= 0) return 0;
     if ((slab & 3) != 0 || (((uintptr_t)part | (uintptr_t)dst) & 15) != 0) {
         long long g = (n + 255) / 256;
         if (g > 4096) g = 4096;
-        hipLaunchKernelGGL(wgrad_reduce_scalar_kernel, dim3((unsigned)g), dim3(256), 0, stream, part, slab, splits, dst, n, g_wgrad_assign ? 1 : 0);
+        hipLaunchKernelGGL(wgrad_reduce_scalar_kernel, dim3((unsigned)g), dim3(256), 0, stream, part, slab, splits, dst, n, assign ? 1 : 0);
         return nkb_check_launch("wgrad_reduce");
     }
     const long long n4 = n >> 2;
@@ -1171,26 +1186,19 @@ int nkb_launch_wgrad_reduce(const float* part, long long slab, int splits, float
     long long grid = (n4 + cols - 1) / cols;
     if (grid > 4096) grid = 4096;
     if (grid < 1) grid = 1;
-    if (g_wgrad_assign) {
-        if (sg == 16) hipLaunchKernelGGL((wgrad_reduce_kernel<16, true>), dim3((unsigned)grid), dim3(256), 0, stream, part, slab, splits, dst, n);
-        else if (sg == 4) hipLaunchKernelGGL((wgrad_reduce_kernel<4, true>), dim3((unsigned)grid), dim3(256), 0, stream, part, slab, splits, dst, n);
-        else hipLaunchKernelGGL((wgrad_reduce_kernel<1, true>), dim3((unsigned)grid), dim3(256), 0, stream, part, slab, splits, dst, n);
-        return nkb_check_launch("wgrad_reduce");
-    }
-    if (sg == 16) hipLaunchKernelGGL(wgrad_reduce_kernel<16>, dim3((unsigned)grid), dim3(256), 0, stream, part, slab, splits, dst, n);
-    else if (sg == 4) hipLaunchKernelGGL(wgrad_reduce_kernel<4>, dim3((unsigned)grid), dim3(256), 0, stream, part, slab, splits, dst, n);
-    else hipLaunchKernelGGL(wgrad_reduce_kernel<1>, dim3((unsigned)grid), dim3(256), 0, stream, part, slab, splits, dst, n);
+    if (assign) launch_wgrad_reduce_kernel<true>(sg, (unsigned)grid, stream, part, slab, splits, dst, n, nullptr, 0, nullptr, 0);
+    else launch_wgrad_reduce_kernel<false>(sg, (unsigned)grid, stream, part, slab, splits, dst, n, nullptr, 0, nullptr, 0);
     return nkb_check_launch("wgrad_reduce");
 }
 // two ranges in one launch (weight slabs + bias partials of one weight gradient); falls back to two launches where the vector form
 // does not apply (unaligned, n2 not a multiple of 4)
 int nkb_launch_wgrad_reduce2(const float* part, long long slab, int splits, float* dst, long long n, const float* part2, long long slab2,
-                             float* dst2, long long n2, hipStream_t stream) {
+                             float* dst2, long long n2, bool assign, hipStream_t stream) {
     if (n <= 0 || splits <= 0) return 0;
     if (n2 <= 0 || (n & 3) || (n2 & 3) || (slab & 3) || (slab2 & 3) ||
         (((uintptr_t)part | (uintptr_t)dst | (uintptr_t)part2 | (uintptr_t)dst2) & 15) != 0) {
-        int rc = nkb_launch_wgrad_reduce(part, slab, splits, dst, n, stream);
-        if (!rc && n2 > 0) rc = nkb_launch_wgrad_reduce(part2, slab2, splits, dst2, n2, stream);
+        int rc = nkb_launch_wgrad_reduce(part, slab, splits, dst, n, assign, stream);
+        if (!rc && n2 > 0) rc = nkb_launch_wgrad_reduce(part2, slab2, splits, dst2, n2, assign, stream);
         return rc;
     }
     const long long t4 = (n + n2) >> 2;
@@ -1198,18 +1206,9 @@ int nkb_launch_wgrad_reduce2(const float* part, long long slab, int splits, floa
     const int cols = 256 / sg;
     long long grid = (t4 + cols - 1) / cols;
     if (grid > 4096) grid = 4096;
-#define W_RED2(SGV, ASG) hipLaunchKernelGGL((wgrad_reduce_kernel<SGV, ASG>), dim3((unsigned)grid), dim3(256), 0, stream, part, slab, splits, dst, n, part2, slab2, dst2, n2)
-    if (g_wgrad_assign) { if (sg == 16) W_RED2(16, true); else if (sg == 4) W_RED2(4, true); else W_RED2(1, true); }
-    else { if (sg == 16) W_RED2(16, false); else if (sg == 4) W_RED2(4, false); else W_RED2(1, false); }
-#undef W_RED2
+    if (assign) launch_wgrad_reduce_kernel<true>(sg, (unsigned)grid, stream, part, slab, splits, dst, n, part2, slab2, dst2, n2);
+    else launch_wgrad_reduce_kernel<false>(sg, (unsigned)grid, stream, part, slab, splits, dst, n, part2, slab2, dst2, n2);
     return nkb_check_launch("wgrad_reduce");
-}
-int nkb_launch_wgrad_reduce_mode(const float* part, long long slab, int splits, float* dst, long long n, int assign, hipStream_t stream) {
-    const bool keep = g_wgrad_assign;
-    g_wgrad_assign = assign != 0;
-    const int rc = nkb_launch_wgrad_reduce(part, slab, splits, dst, n, stream);
-    g_wgrad_assign = keep;
-    return rc;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1222,17 +1221,17 @@ static int launch_conv_impl(ConvParams& p, hipStream_t stream, int batch) {
         // When the whole filter matrix does not fit next to the activation rows in one XCD's L2 (4 MB), walking "all channel
         // tiles of a few row tiles" streams the filter through L2 once per row tile.  Groups of 8 row tiles keep 8 activation
         // tiles resident and let each filter tile serve 8 workgroups at once.
-        constexpr int gm_env = 8;
+        constexpr int GROUP_ROW_TILES = 8;
         const double wbytes = (double)p.Cout * p.R * p.S * p.Cin * sizeof(T);
         // (measured, ViT-B/16 shapes: N = 3072 334.9 -> 316.2 us, N = 2304 282.5 -> 274.9; with <= 6 channel tiles all of them are
         // resident at once either way and the grouped walk is 1-2 % slower, so it only engages for wide outputs)
-        constexpr int gm_min_n = 12;
-        p.group_m = (gm_env > 1 && batch == 1 && wbytes > 3.0e6 && p.tilesN >= gm_min_n && p.tilesM >= 2 * gm_env) ? gm_env : 0;
+        constexpr int GROUP_MIN_CHANNEL_TILES = 12;
+        p.group_m = (batch == 1 && wbytes > 3.0e6 && p.tilesN >= GROUP_MIN_CHANNEL_TILES && p.tilesM >= 2 * GROUP_ROW_TILES) ? GROUP_ROW_TILES : 0;
     }
     constexpr int xrows = HALO ? 32 * ((TP + 2 + 31) / 32) : TP;
     constexpr int stage = (TC + xrows) * 128;
     constexpr int epi = (TP / 2) * (TC * 4 + 16);
-    constexpr int lds = (stage > epi ? stage : epi) + ((BNB == 1 || BNB == 2 || BNB == 6 || BNB == 7) ? 3 * TC * 4 : 0);
+    constexpr int lds = (stage > epi ? stage : epi) + ((BNB == EPI_BN_MASK || BNB == EPI_BN_BITS || BNB == EPI_BN_BITS_LEAN || BNB == EPI_BN_MASK_LEAN) ? 3 * TC * 4 : 0);
     static bool attr_set = false;
     if (!attr_set) {
         hipFuncSetAttribute((const void*)conv_igemm_kernel<T, TC, TP, BNB, HALO>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -1243,42 +1242,81 @@ static int launch_conv_impl(ConvParams& p, hipStream_t stream, int batch) {
     return nkb_check_launch("conv_igemm");
 }
 
-template <typename T, int TC, int TP, int BNB = 0>
-static int launch_conv(ConvParams& p, hipStream_t stream, int batch = 1);
-// BNB == 1 launches: the lean instantiation (BNB == 7) when the geometry is the common one
-template <typename T, int TC, int TP>
-static int launch_conv_bn1(ConvParams& p, hipStream_t stream) {
-    if constexpr (sizeof(T) == 2) {
-        constexpr int lean1 = 1;
-        if (lean1 && p.sub_h == 0 && p.add == nullptr && (p.ldy & 7) == 0 && (p.Cout & 7) == 0 && p.stats != nullptr && p.aux != nullptr)
-            return launch_conv<T, TC, TP, 7>(p, stream);
+// whether a bf16 launch that asks for epilogue BNB can take that epilogue's lean instantiation
+template <int BNB>
+static bool lean_epilogue_ok(const ConvParams& p) {
+    if constexpr (BNB == EPI_GENERAL) {
+        // EPI_LEAN: the launch has nothing but bias / ReLU / statistics (or a plain full-grid residual) to do
+        const bool add_ok = p.add == nullptr || (p.stats == nullptr && p.add_h == 0 && p.add_bits == nullptr && (p.ldadd & 7) == 0);
+        return add_ok && p.act == 0 && p.sub_h == 0 && !p.out_f32 && (p.Cout & 7) == 0 && (p.ldy & 7) == 0;
+    } else if constexpr (BNB == EPI_BN_MASK) {
+        // EPI_BN_MASK_LEAN: the common geometry (no residual, no parity-class remap, 8-channel-aligned rows)
+        return p.sub_h == 0 && p.add == nullptr && (p.ldy & 7) == 0 && (p.Cout & 7) == 0 && p.stats != nullptr && p.aux != nullptr;
+    } else {
+        // EPI_BN_BITS_LEAN: the common geometry (full-grid residual, 8-channel-aligned rows)
+        static_assert(BNB == EPI_BN_BITS, "no lean instantiation for this epilogue");
+        return p.add != nullptr && (p.add_h == 0 || p.add_bits == nullptr) && (p.ldy & 7) == 0 && (p.ldadd & 7) == 0 && (p.Cout & 7) == 0 &&
+               p.stats != nullptr;
     }
-    return launch_conv<T, TC, TP, 1>(p, stream);
 }
+static bool halo_switch() {
+    static const int halo_on = [] { const char* e = getenv("NKB_HALO"); return e ? atoi(e) : 1; }();
+    return halo_on != 0;
+}
+// one tile shape: the lean instantiation of the epilogue where the launch qualifies (bf16), then HALO or not
 template <typename T, int TC, int TP, int BNB>
-static int launch_conv(ConvParams& p, hipStream_t stream, int batch) {
+static int launch_conv_tile(ConvParams& p, hipStream_t stream, int batch) {
     if constexpr (sizeof(T) == 2) {
+        constexpr int LEAN = BNB == EPI_GENERAL ? EPI_LEAN : BNB == EPI_BN_MASK ? EPI_BN_MASK_LEAN : BNB == EPI_BN_BITS ? EPI_BN_BITS_LEAN : BNB;
+        if constexpr (LEAN != BNB) {
+            if (lean_epilogue_ok<BNB>(p)) return launch_conv_tile<T, TC, TP, LEAN>(p, stream, batch);
+        }
         // 3x3 / stride 1 / pad 1 (forward and data gradient): the filter-row-sharing form, 3 activation tiles per
         // channel chunk instead of 9
-        static const int halo_on = [] { const char* e = getenv("NKB_HALO"); return e ? atoi(e) : 1; }();
-        if (halo_on && p.R == 3 && p.S == 3 && p.stride == 1 && p.stride_w == 1 && p.pad == 1 && p.pad_w == 1 &&
+        if (halo_switch() && p.R == 3 && p.S == 3 && p.stride == 1 && p.stride_w == 1 && p.pad == 1 && p.pad_w == 1 &&
             p.stem_cprw == 0 && p.sub_h == 0 && p.H == p.P && p.W == p.Q)
             return launch_conv_impl<T, TC, TP, BNB, true>(p, stream, batch);
     }
     return launch_conv_impl<T, TC, TP, BNB, false>(p, stream, batch);
 }
-
-// picks the lean-epilogue instantiation (BNB = 3) when the launch has nothing but bias / ReLU / statistics to do
-template <typename T, int TC, int TP>
-static int launch_conv_auto(ConvParams& p, hipStream_t stream, int batch = 1) {
-    if constexpr (sizeof(T) == 2) {
-        constexpr int lean_on = 1;
-        const bool add_ok = p.add == nullptr || (p.stats == nullptr && p.add_h == 0 && p.add_bits == nullptr && (p.ldadd & 7) == 0);
-        const bool plain = lean_on && add_ok && p.act == 0 && p.sub_h == 0 && !p.out_f32 && (p.Cout & 7) == 0 &&
-                           (p.ldy & 7) == 0;
-        if (plain) return launch_conv<T, TC, TP, 3>(p, stream, batch);
+// The 64 x 256 tile instead of the 128 x 128 one for outputs of at most 64 channels.  NKB_NARROW=0 switches it off for the convolution
+// entry points (and for nkb_conv_gemm_stat_tiles, which sizes the statistics buffer their kernels write); nkb_linear_gelu,
+// nkb_gemm_batched and nkb_stem_conv never looked at the switch and go by the channel count alone (honour_switch = false).
+static bool narrow_tile(int Cout, bool honour_switch = true) {
+    static const int narrow_on = [] { const char* e = getenv("NKB_NARROW"); return e ? atoi(e) : 1; }();
+    return Cout <= 64 && (narrow_on || !honour_switch);
+}
+// The one dispatch: (dtype, narrow) picks <T, TC, TP>; BNB is the epilogue the entry point asks for (launch_conv_tile may take its
+// lean instantiation).  EPI_AFFINE_BITS and EPI_LEAN_CAT exist in bf16 only, the former in the 128 x 128 tile only (its entry points
+// require Cout > 64).
+template <int BNB>
+static int launch_conv(ConvParams& p, int dtype, bool narrow, hipStream_t stream, int batch = 1) {
+    if constexpr (BNB != EPI_AFFINE_BITS && BNB != EPI_LEAN_CAT) {
+        if (dtype != NKB_DT_BF16)
+            return narrow ? launch_conv_tile<float, 64, 256, BNB>(p, stream, batch) : launch_conv_tile<float, 128, 128, BNB>(p, stream, batch);
     }
-    return launch_conv<T, TC, TP, 0>(p, stream, batch);
+    if constexpr (BNB != EPI_AFFINE_BITS) {
+        if (narrow) return launch_conv_tile<bf16_t, 64, 256, BNB>(p, stream, batch);
+    }
+    return launch_conv_tile<bf16_t, 128, 128, BNB>(p, stream, batch);
+}
+
+// parameter block of a convolution: geometry, M, filter row stride, the fast divisions; everything else at its default
+static ConvParams conv_geometry(int N, int H, int W, int Cin, int ldx, int P, int Q, int Cout, int ldy, int R, int S, int stride, int pad,
+                                int mode) {
+    ConvParams p;
+    p.M = N * P * Q; p.H = H; p.W = W; p.Cin = Cin; p.ldx = ldx; p.P = P; p.Q = Q; p.Cout = Cout; p.ldy = ldy;
+    p.R = R; p.S = S; p.stride = stride; p.pad = pad; p.mode = mode;
+    p.stride_w = stride; p.pad_w = pad;
+    p.divPQ = make_fastdiv((unsigned)(P * Q)); p.divQ = make_fastdiv((unsigned)Q);
+    p.ldw = R * S * Cin;
+    return p;
+}
+// parameter block of a plain row-major product y[M][N] = x[M][K] . w[N][K]^T: a 1x1 convolution over an M x 1 image
+static ConvParams gemm_geometry(int M, int K, int N, int ldx, int ldw, int ldy) {
+    ConvParams p = conv_geometry(1, M, 1, K, ldx, M, 1, N, ldy, 1, 1, 1, 0, 0);
+    p.ldw = ldw;
+    return p;
 }
 
 extern "C" int nkb_conv_gemm(int dtype, int mode, const void* x, const void* w, void* y, const void* add,
@@ -1303,27 +1341,18 @@ extern "C" int nkb_conv_gemm(int dtype, int mode, const void* x, const void* w, 
         nkb_set_error("conv_gemm: tensor exceeds 2^31 elements");
         return 1;
     }
-    ConvParams p;
-    p.x = x; p.w = w; p.y = y; p.add = add; p.bias = bias; p.stats = stats;
-    p.M = N * P * Q; p.H = H; p.W = W; p.Cin = Cin; p.ldx = ldx; p.P = P; p.Q = Q; p.Cout = Cout; p.ldy = ldy;
-    p.ldadd = ldadd; p.R = R; p.S = S; p.stride = stride; p.pad = pad; p.mode = mode; p.relu = relu;
-    p.stride_w = stride; p.pad_w = pad; p.stem_cprw = 0;
-    p.out_f32 = out_f32;
-    p.divPQ = make_fastdiv((unsigned)(P * Q)); p.divQ = make_fastdiv((unsigned)Q);
-    p.ldw = R * S * Cin; p.inner = 1; p.sxo = p.sxi = p.swo = p.swi = p.syo = p.syi = 0;
-    p.add_h = add_h; p.add_w = add_w; p.act = 0; p.aux = nullptr; p.y2 = nullptr;
     if (add_bits && (add == nullptr || add_h > 0 || ldadd % 8 != 0)) { nkb_set_error("conv_gemm: add_bits needs a full-grid add with ldadd %% 8 == 0"); return 1; }
-    p.add_bits = add_bits;
+    ConvParams p = conv_geometry(N, H, W, Cin, ldx, P, Q, Cout, ldy, R, S, stride, pad, mode);
+    p.x = x; p.w = w; p.y = y; p.add = add; p.bias = bias; p.stats = stats;
+    p.ldadd = ldadd; p.relu = relu; p.out_f32 = out_f32;
+    p.add_h = add_h; p.add_w = add_w; p.add_bits = add_bits;
     const double flops = 2.0 * p.M * (double)Cout * R * S * Cin;
     // algorithmic bytes: every operand element once (source image, filter, destination, residual operand)
     const double bytes = ((double)N * H * W * Cin + (double)Cout * R * S * Cin) * esz +
                          (double)p.M * Cout * (out_f32 ? 4 : esz) * (add ? 2 : 1);
     NkbProfScope prof(mode == 0 ? NKB_K_CONV_FWD : NKB_K_CONV_DGRAD, stream, flops, bytes);
     if (nkb_gemm8p_eligible(p, dtype, 1)) return nkb_launch_gemm8p(p, stream);       // wide plain GEMMs: 256^2 eight-phase core
-    static const int narrow_on = [] { const char* e = getenv("NKB_NARROW"); return e ? atoi(e) : 1; }();
-    const bool narrow = Cout <= 64 && narrow_on;
-    if (dtype == NKB_DT_BF16) return narrow ? launch_conv_auto<bf16_t, 64, 256>(p, stream) : launch_conv_auto<bf16_t, 128, 128>(p, stream);
-    return narrow ? launch_conv_auto<float, 64, 256>(p, stream) : launch_conv_auto<float, 128, 128>(p, stream);
+    return launch_conv<EPI_GENERAL>(p, dtype, narrow_tile(Cout), stream);
 }
 
 // Data gradient of a convolution whose input was relu(bn(c)): same contraction as nkb_conv_gemm(mode 1), but the epilogue
@@ -1350,37 +1379,19 @@ extern "C" int nkb_conv_dgrad_bn(int dtype, const void* dy, const void* w, void*
         nkb_set_error("conv_dgrad_bn: operand exceeds the addressing range");
         return 1;
     }
-    ConvParams p;
     if (relu_bits == nullptr && (add != nullptr || scale == nullptr || shift == nullptr)) {
         nkb_set_error("conv_dgrad_bn: the recomputed-mask form takes scale/shift and no residual operand");
         return 1;
     }
     if (add && ((add_h == 0 && ldadd % 8 != 0) || (add_bits && add_h > 0))) { nkb_set_error("conv_dgrad_bn: bad add operand (ldadd=%d)", ldadd); return 1; }
-    p.x = dy; p.w = w; p.y = g_masked; p.add = add; p.bias = nullptr; p.stats = stats;
-    p.M = N * P * Q; p.H = H; p.W = W; p.Cin = Cin; p.ldx = ldx; p.P = P; p.Q = Q; p.Cout = Cout; p.ldy = ldy;
-    p.ldadd = ldadd; p.R = R; p.S = S; p.stride = stride; p.pad = pad; p.mode = 1; p.relu = 0;
-    p.stride_w = stride; p.pad_w = pad; p.stem_cprw = 0;
-    p.out_f32 = 0;
-    p.divPQ = make_fastdiv((unsigned)(P * Q)); p.divQ = make_fastdiv((unsigned)Q);
-    p.ldw = R * S * Cin; p.inner = 1; p.sxo = p.sxi = p.swo = p.swi = p.syo = p.syi = 0;
-    p.add_h = add_h; p.add_w = add_w; p.act = 0; p.aux = c; p.y2 = nullptr;
-    p.add_bits = add_bits; p.bn_bits = relu_bits;
-    p.bn_scale = scale; p.bn_shift = shift; p.bn_mean = mean;
+    ConvParams p = conv_geometry(N, H, W, Cin, ldx, P, Q, Cout, ldy, R, S, stride, pad, 1);
+    p.x = dy; p.w = w; p.y = g_masked; p.add = add; p.stats = stats; p.aux = c;
+    p.ldadd = ldadd; p.add_h = add_h; p.add_w = add_w; p.add_bits = add_bits;
+    p.bn_bits = relu_bits; p.bn_scale = scale; p.bn_shift = shift; p.bn_mean = mean;
     NkbProfScope prof(NKB_K_CONV_DGRAD, stream, 2.0 * p.M * (double)Cout * R * S * Cin,
                       ((double)N * H * W * Cin + (double)Cout * R * S * Cin + ((add ? 2.0 : 1.0) + (c ? 1.0 : 0.0)) * p.M * Cout) * esz);
-    static const int narrow_on = [] { const char* e = getenv("NKB_NARROW"); return e ? atoi(e) : 1; }();
-    const bool narrow = Cout <= 64 && narrow_on;
-    if (relu_bits) {
-        // lean epilogue instantiation for the common geometry (full-grid residual, 8-channel-aligned rows)
-        constexpr int lean2 = 1;
-        if (lean2 && dtype == NKB_DT_BF16 && add != nullptr && (add_h == 0 || add_bits == nullptr) && (ldy & 7) == 0 && (ldadd & 7) == 0 &&
-            (Cout & 7) == 0 && stats != nullptr)
-            return narrow ? launch_conv<bf16_t, 64, 256, 6>(p, stream) : launch_conv<bf16_t, 128, 128, 6>(p, stream);
-        if (dtype == NKB_DT_BF16) return narrow ? launch_conv<bf16_t, 64, 256, 2>(p, stream) : launch_conv<bf16_t, 128, 128, 2>(p, stream);
-        return narrow ? launch_conv<float, 64, 256, 2>(p, stream) : launch_conv<float, 128, 128, 2>(p, stream);
-    }
-    if (dtype == NKB_DT_BF16) return narrow ? launch_conv_bn1<bf16_t, 64, 256>(p, stream) : launch_conv_bn1<bf16_t, 128, 128>(p, stream);
-    return narrow ? launch_conv<float, 64, 256, 1>(p, stream) : launch_conv<float, 128, 128, 1>(p, stream);
+    if (relu_bits) return launch_conv<EPI_BN_BITS>(p, dtype, narrow_tile(Cout), stream);
+    return launch_conv<EPI_BN_MASK>(p, dtype, narrow_tile(Cout), stream);
 }
 
 // Closing stage of a residual block with the BatchNorm statistics known before the launch (Gram form, grambn.hip):
@@ -1402,19 +1413,13 @@ extern "C" int nkb_conv_affine_residual(int dtype, const void* x, const void* w,
         nkb_set_error("conv_affine_residual: operand exceeds the addressing range");
         return 1;
     }
-    ConvParams p;
-    p.x = x; p.w = w; p.y = y; p.add = res; p.bias = shift; p.stats = nullptr;
-    p.M = N * P * Q; p.H = H; p.W = W; p.Cin = Cin; p.ldx = ldx; p.P = P; p.Q = Q; p.Cout = Cout; p.ldy = ldy;
-    p.ldadd = ldres; p.R = R; p.S = S; p.stride = stride; p.pad = pad; p.mode = 0; p.relu = 1;
-    p.stride_w = stride; p.pad_w = pad; p.stem_cprw = 0; p.out_f32 = 0;
-    p.divPQ = make_fastdiv((unsigned)(P * Q)); p.divQ = make_fastdiv((unsigned)Q);
-    p.ldw = R * S * Cin; p.inner = 1; p.sxo = p.sxi = p.swo = p.swi = p.syo = p.syi = 0;
-    p.add_h = 0; p.add_w = 0; p.act = 0; p.aux = nullptr; p.y2 = nullptr;
+    ConvParams p = conv_geometry(N, H, W, Cin, ldx, P, Q, Cout, ldy, R, S, stride, pad, 0);
+    p.x = x; p.w = w; p.y = y; p.add = res; p.ldadd = ldres; p.bias = shift; p.relu = 1;
     p.oscale = scale; p.add_scale = res_scale; p.add_shift = res_shift; p.out_bits = relu_bits;
     nkb_count_launch(4);
     NkbProfScope prof(NKB_K_CONV_FWD, stream, 2.0 * p.M * (double)Cout * R * S * Cin,
                       ((double)N * H * W * Cin + (double)Cout * R * S * Cin + 2.0 * p.M * Cout) * 2 + (double)p.M * Cout / 8);
-    return launch_conv<bf16_t, 128, 128, 4>(p, stream);
+    return launch_conv<EPI_AFFINE_BITS>(p, dtype, false, stream);
 }
 
 // Gram-form closing stage of a block WITH a projection shortcut (stride 1): both BatchNorms' scales are folded into ONE filter,
@@ -1428,20 +1433,13 @@ extern "C" int nkb_conv_cat_relu_bits(int dtype, const void* a, int lda, int K1,
         return 1;
     }
     if (M * lda * 2 >= 0xFFFFFF00ll || M * ldx * 2 >= 0xFFFFFF00ll || M * ldy >= (1ll << 31)) { nkb_set_error("conv_cat_relu_bits: operand too large"); return 1; }
-    ConvParams p;
-    p.x = a; p.w = wf; p.y = y; p.add = nullptr; p.bias = shift; p.stats = nullptr;
-    p.M = (int)M; p.H = (int)M; p.W = 1; p.Cin = K1 + K2; p.ldx = lda; p.P = (int)M; p.Q = 1; p.Cout = Cout; p.ldy = ldy;
-    p.ldadd = 0; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0; p.mode = 0; p.relu = 1;
-    p.stride_w = 1; p.pad_w = 0; p.stem_cprw = 0; p.out_f32 = 0;
-    p.divPQ = make_fastdiv((unsigned)M); p.divQ = make_fastdiv(1u);
-    p.ldw = K1 + K2; p.inner = 1; p.sxo = p.sxi = p.swo = p.swi = p.syo = p.syi = 0;
-    p.add_h = 0; p.add_w = 0; p.act = 0; p.aux = nullptr; p.y2 = nullptr;
-    p.oscale = nullptr; p.add_scale = nullptr; p.add_shift = nullptr; p.out_bits = relu_bits;
+    ConvParams p = gemm_geometry((int)M, K1 + K2, Cout, lda, K1 + K2, ldy);
+    p.x = a; p.w = wf; p.y = y; p.bias = shift; p.relu = 1; p.out_bits = relu_bits;
     p.x2 = x; p.ldx2 = ldx; p.kt2 = K1 / 64;
     nkb_count_launch(4);
     NkbProfScope prof(NKB_K_CONV_FWD, stream, 2.0 * M * (double)Cout * (K1 + K2),
                       ((double)M * (K1 + K2) + (double)Cout * (K1 + K2) + (double)M * Cout) * 2 + (double)M * Cout / 8);
-    return launch_conv<bf16_t, 128, 128, 4>(p, stream);
+    return launch_conv<EPI_AFFINE_BITS>(p, dtype, false, stream);
 }
 // y = [a | x] . w^T + bias, plain bf16 store: the shortcut's input gradient in the Gram form, dx = [g | x] . [k1 Wd ; Qd] + k3 Wd.
 extern "C" int nkb_conv_cat_bias(int dtype, const void* a, int lda, int K1, const void* x, int ldx, int K2, const void* w, const float* bias,
@@ -1451,18 +1449,11 @@ extern "C" int nkb_conv_cat_bias(int dtype, const void* a, int lda, int K1, cons
         return 1;
     }
     if (M * lda * 2 >= 0xFFFFFF00ll || M * ldx * 2 >= 0xFFFFFF00ll || M * ldy >= (1ll << 31)) { nkb_set_error("conv_cat_bias: operand too large"); return 1; }
-    ConvParams p;
-    p.x = a; p.w = w; p.y = y; p.add = nullptr; p.bias = bias; p.stats = nullptr;
-    p.M = (int)M; p.H = (int)M; p.W = 1; p.Cin = K1 + K2; p.ldx = lda; p.P = (int)M; p.Q = 1; p.Cout = Cout; p.ldy = ldy;
-    p.ldadd = 0; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0; p.mode = 1; p.relu = 0;
-    p.stride_w = 1; p.pad_w = 0; p.stem_cprw = 0; p.out_f32 = 0;
-    p.divPQ = make_fastdiv((unsigned)M); p.divQ = make_fastdiv(1u);
-    p.ldw = K1 + K2; p.inner = 1; p.sxo = p.sxi = p.swo = p.swi = p.syo = p.syi = 0;
-    p.add_h = 0; p.add_w = 0; p.act = 0; p.aux = nullptr; p.y2 = nullptr;
+    ConvParams p = gemm_geometry((int)M, K1 + K2, Cout, lda, K1 + K2, ldy);
+    p.x = a; p.w = w; p.y = y; p.bias = bias; p.mode = 1;
     p.x2 = x; p.ldx2 = ldx; p.kt2 = K1 / 64;
     NkbProfScope prof(NKB_K_CONV_DGRAD, stream, 2.0 * M * (double)Cout * (K1 + K2), ((double)M * (K1 + K2) + (double)Cout * (K1 + K2) + (double)M * Cout) * 2);
-    static const int narrow_on = [] { const char* e = getenv("NKB_NARROW"); return e ? atoi(e) : 1; }();
-    return (Cout <= 64 && narrow_on) ? launch_conv<bf16_t, 64, 256, 8>(p, stream) : launch_conv<bf16_t, 128, 128, 8>(p, stream);
+    return launch_conv<EPI_LEAN_CAT>(p, dtype, narrow_tile(Cout), stream);
 }
 
 // Data gradient of the Gram-form closing stage (grambn.hip): with dc = k1*g + k2*c + k3 and c = a W^T never materialised,
@@ -1485,22 +1476,13 @@ extern "C" int nkb_conv_dgrad_bn_cat(int dtype, const void* g, int ldg, int K1, 
         nkb_set_error("conv_dgrad_bn_cat: operand exceeds the addressing range");
         return 1;
     }
-    ConvParams p;
-    p.x = g; p.w = wcat; p.y = g_masked; p.add = nullptr; p.bias = cbias; p.stats = stats;
-    p.M = (int)M; p.H = (int)M; p.W = 1; p.Cin = K1 + K2; p.ldx = ldg; p.P = (int)M; p.Q = 1; p.Cout = Cout; p.ldy = ldy;
-    p.ldadd = 0; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0; p.mode = 1; p.relu = 0;
-    p.stride_w = 1; p.pad_w = 0; p.stem_cprw = 0; p.out_f32 = 0;
-    p.divPQ = make_fastdiv((unsigned)M); p.divQ = make_fastdiv(1u);
-    p.ldw = K1 + K2; p.inner = 1; p.sxo = p.sxi = p.swo = p.swi = p.syo = p.syi = 0;
-    p.add_h = 0; p.add_w = 0; p.act = 0; p.aux = c_prev; p.y2 = nullptr;
+    ConvParams p = gemm_geometry((int)M, K1 + K2, Cout, ldg, K1 + K2, ldy);
+    p.x = g; p.w = wcat; p.y = g_masked; p.bias = cbias; p.stats = stats; p.mode = 1; p.aux = c_prev;
     p.bn_scale = scale; p.bn_shift = shift; p.bn_mean = mean;
     p.x2 = a; p.ldx2 = lda; p.kt2 = K1 / kte;
     NkbProfScope prof(NKB_K_CONV_DGRAD, stream, 2.0 * M * (double)Cout * (K1 + K2),
                       ((double)M * (K1 + K2) + (double)Cout * (K1 + K2) + 2.0 * M * Cout) * esz);
-    static const int narrow_on = [] { const char* e = getenv("NKB_NARROW"); return e ? atoi(e) : 1; }();
-    const bool narrow = Cout <= 64 && narrow_on;
-    if (dtype == NKB_DT_BF16) return narrow ? launch_conv_bn1<bf16_t, 64, 256>(p, stream) : launch_conv_bn1<bf16_t, 128, 128>(p, stream);
-    return narrow ? launch_conv<float, 64, 256, 1>(p, stream) : launch_conv<float, 128, 128, 1>(p, stream);
+    return launch_conv<EPI_BN_MASK>(p, dtype, narrow_tile(Cout), stream);
 }
 
 // The same closing-stage data gradient in two launches, so that everything that depends on the gradient statistics can run BESIDE
@@ -1521,20 +1503,11 @@ extern "C" int nkb_conv_dgrad_bn_add(int dtype, const void* a, int lda, int K, c
         nkb_set_error("conv_dgrad_bn_add: operand exceeds the addressing range");
         return 1;
     }
-    ConvParams p;
-    p.x = a; p.w = q; p.y = g_masked; p.add = t; p.bias = cbias; p.stats = stats;
-    p.M = (int)M; p.H = (int)M; p.W = 1; p.Cin = K; p.ldx = lda; p.P = (int)M; p.Q = 1; p.Cout = Cout; p.ldy = ldy;
-    p.ldadd = ldt; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0; p.mode = 1; p.relu = 0;
-    p.stride_w = 1; p.pad_w = 0; p.stem_cprw = 0; p.out_f32 = 0;
-    p.divPQ = make_fastdiv((unsigned)M); p.divQ = make_fastdiv(1u);
-    p.ldw = K; p.inner = 1; p.sxo = p.sxi = p.swo = p.swi = p.syo = p.syi = 0;
-    p.add_h = 0; p.add_w = 0; p.act = 0; p.aux = c_prev; p.y2 = nullptr;
+    ConvParams p = gemm_geometry((int)M, K, Cout, lda, K, ldy);
+    p.x = a; p.w = q; p.y = g_masked; p.add = t; p.ldadd = ldt; p.bias = cbias; p.stats = stats; p.mode = 1; p.aux = c_prev;
     p.bn_scale = scale; p.bn_shift = shift; p.bn_mean = mean;
     NkbProfScope prof(NKB_K_CONV_DGRAD, stream, 2.0 * M * (double)Cout * K, ((double)M * K + (double)Cout * K + 3.0 * M * Cout) * esz);
-    static const int narrow_on = [] { const char* e = getenv("NKB_NARROW"); return e ? atoi(e) : 1; }();
-    const bool narrow = Cout <= 64 && narrow_on;
-    if (dtype == NKB_DT_BF16) return narrow ? launch_conv_bn1<bf16_t, 64, 256>(p, stream) : launch_conv_bn1<bf16_t, 128, 128>(p, stream);
-    return narrow ? launch_conv<float, 64, 256, 1>(p, stream) : launch_conv<float, 128, 128, 1>(p, stream);
+    return launch_conv<EPI_BN_MASK>(p, dtype, narrow_tile(Cout), stream);
 }
 
 // One parity class of the data gradient of a 3x3 / stride-2 / pad-1 convolution.  Output pixels (h, w) with
@@ -1564,28 +1537,17 @@ extern "C" int nkb_conv_dgrad_s2class(int dtype, const void* dy, const void* w_c
         nkb_set_error("conv_dgrad_s2class: sub-grid add must be [N][ceil(H/2)][ceil(W/2)]");
         return 1;
     }
-    ConvParams p;
-    p.x = dy; p.w = w_class; p.y = y; p.add = c ? nullptr : add; p.bias = nullptr; p.stats = stats;
-    p.M = N * Pc * Qc; p.H = Hdy; p.W = Wdy; p.Cin = K; p.ldx = ldx; p.P = Pc; p.Q = Qc; p.Cout = C; p.ldy = ldy;
-    p.ldadd = ldadd; p.R = Rc; p.S = Sc; p.stride = 1; p.pad = ph; p.mode = 1; p.relu = 0;   // pad' = (ph+1-r0)/2 = ph
-    p.stride_w = 1; p.pad_w = pw; p.stem_cprw = 0;
-    p.out_f32 = 0;
-    p.divPQ = make_fastdiv((unsigned)(Pc * Qc)); p.divQ = make_fastdiv((unsigned)Qc);
-    p.ldw = Rc * Sc * K; p.inner = 1; p.sxo = p.sxi = p.swo = p.swi = p.syo = p.syi = 0;
-    p.add_h = add_h; p.add_w = add_w; p.act = 0; p.aux = c; p.y2 = nullptr;
+    ConvParams p = conv_geometry(N, Hdy, Wdy, K, ldx, Pc, Qc, C, ldy, Rc, Sc, 1, ph, 1);   // pad' = (ph+1-r0)/2 = ph
+    p.pad_w = pw;
+    p.x = dy; p.w = w_class; p.y = y; p.add = c ? nullptr : add; p.stats = stats; p.aux = c;
+    p.ldadd = ldadd; p.add_h = add_h; p.add_w = add_w;
     p.bn_scale = scale; p.bn_shift = shift; p.bn_mean = mean;
     p.sub_h = Hout; p.sub_w = Wout; p.sub_ph = ph; p.sub_pw = pw;
     const double flops = 2.0 * p.M * (double)C * Rc * Sc * K;
     const double bytes = ((double)N * Hdy * Wdy * K / 4.0 + (double)C * Rc * Sc * K + (double)p.M * C * ((add || c) ? 2 : 1)) * esz;
     NkbProfScope prof(NKB_K_CONV_DGRAD, stream, flops, bytes);
-    static const int narrow_on = [] { const char* e = getenv("NKB_NARROW"); return e ? atoi(e) : 1; }();
-    const bool narrow = C <= 64 && narrow_on;
-    if (c) {
-        if (dtype == NKB_DT_BF16) return narrow ? launch_conv_bn1<bf16_t, 64, 256>(p, stream) : launch_conv_bn1<bf16_t, 128, 128>(p, stream);
-        return narrow ? launch_conv<float, 64, 256, 1>(p, stream) : launch_conv<float, 128, 128, 1>(p, stream);
-    }
-    if (dtype == NKB_DT_BF16) return narrow ? launch_conv_auto<bf16_t, 64, 256>(p, stream) : launch_conv_auto<bf16_t, 128, 128>(p, stream);
-    return narrow ? launch_conv_auto<float, 64, 256>(p, stream) : launch_conv_auto<float, 128, 128>(p, stream);
+    if (c) return launch_conv<EPI_BN_MASK>(p, dtype, narrow_tile(C), stream);
+    return launch_conv<EPI_GENERAL>(p, dtype, narrow_tile(C), stream);
 }
 
 // Linear layer with a fused exact-erf GELU epilogue (timm ViT MLP):
@@ -1596,20 +1558,10 @@ extern "C" int nkb_conv_dgrad_s2class(int dtype, const void* dy, const void* w_c
 //   act 4: y = (x W^T) * aux                                  (fc2 data-gradient, aux = gelu'(pre) from nkb_gelu_fwd_dgelu)
 //   act 5: pre = x W^T + b -> y = gelu(pre), y2 = gelu'(pre)  (fc1 forward when the backward pass is act 4: the pre-activation is
 //          never stored and the separate nkb_gelu_fwd_dgelu pass disappears; eight-phase core only — nkb_linear_gelu_fused_ok)
-static void linear_gelu_params(ConvParams& p, int act, const void* x, const void* w, const float* bias, const void* aux, void* y,
-                               void* y2, int M, int K, int N) {
-    p.x = x; p.w = w; p.y = y; p.add = nullptr; p.bias = bias; p.stats = nullptr;
-    p.M = M; p.H = M; p.W = 1; p.Cin = K; p.ldx = K; p.P = M; p.Q = 1; p.Cout = N; p.ldy = N; p.ldadd = 0;
-    p.R = 1; p.S = 1; p.stride = 1; p.pad = 0; p.mode = 0; p.relu = 0; p.out_f32 = 0;
-    p.stride_w = 1; p.pad_w = 0; p.stem_cprw = 0;
-    p.divPQ = make_fastdiv((unsigned)M); p.divQ = make_fastdiv(1u);
-    p.add_h = 0; p.add_w = 0; p.act = act; p.aux = aux; p.y2 = y2;
-    p.ldw = K; p.inner = 1; p.sxo = p.sxi = p.swo = p.swi = p.syo = p.syi = 0;
-}
 extern "C" int nkb_linear_gelu_fused_ok(int dtype, int M, int K, int N) {
     if (dtype != NKB_DT_BF16 || (long long)M * K * 2 >= 0xFFFFFF00ll || (long long)N * K * 2 >= 0xFFFFFF00ll || (long long)M * N >= (1ll << 31)) return 0;
-    ConvParams p;
-    linear_gelu_params(p, 5, nullptr, nullptr, nullptr, nullptr, nullptr, (void*)16, M, K, N);
+    ConvParams p = gemm_geometry(M, K, N, K, K, N);
+    p.act = 5; p.y2 = (void*)16;
     return nkb_gemm8p_eligible(p, dtype, 1) ? 1 : 0;
 }
 // y = add + row_scale[m / rows_per_sample] * (x W^T + b): a residual branch under per-sample stochastic depth (the unicom blocks'
@@ -1621,9 +1573,8 @@ extern "C" int nkb_linear_residual_scaled(int dtype, const void* x, const void* 
         nkb_set_error("linear_residual_scaled: needs add, row_scale, rows_per_sample >= 1 and a bf16 shape of the eight-phase core");
         return 1;
     }
-    ConvParams p;
-    linear_gelu_params(p, 0, x, w, bias, nullptr, y, nullptr, M, K, N);
-    p.add = add; p.ldadd = N;
+    ConvParams p = gemm_geometry(M, K, N, K, K, N);
+    p.x = x; p.w = w; p.y = y; p.bias = bias; p.add = add; p.ldadd = N;
     if (!nkb_gemm8p_eligible(p, dtype, 1)) { nkb_set_error("linear_residual_scaled: shape not eligible"); return 1; }
     NkbProfScope prof(NKB_K_CONV_FWD, stream, 2.0 * M * (double)N * K);
     return nkb_launch_gemm8p(p, stream, row_scale, rows_per_sample);
@@ -1644,13 +1595,11 @@ extern "C" int nkb_linear_gelu(int dtype, int act, const void* x, const void* w,
         nkb_set_error("linear_gelu: operand exceeds the 4 GiB buffer-addressing range");
         return 1;
     }
-    ConvParams p;
-    linear_gelu_params(p, act, x, w, bias, aux, y, y2, M, K, N);
+    ConvParams p = gemm_geometry(M, K, N, K, K, N);
+    p.x = x; p.w = w; p.y = y; p.bias = bias; p.act = act; p.aux = aux; p.y2 = y2;
     NkbProfScope prof(act == 1 || act == 5 ? NKB_K_CONV_FWD : NKB_K_CONV_DGRAD, stream, 2.0 * M * (double)N * K);
     if (nkb_gemm8p_eligible(p, dtype, 1)) return nkb_launch_gemm8p(p, stream);
-    const bool narrow = N <= 64;
-    if (dtype == NKB_DT_BF16) return narrow ? launch_conv_auto<bf16_t, 64, 256>(p, stream) : launch_conv_auto<bf16_t, 128, 128>(p, stream);
-    return narrow ? launch_conv_auto<float, 64, 256>(p, stream) : launch_conv_auto<float, 128, 128>(p, stream);
+    return launch_conv<EPI_GENERAL>(p, dtype, narrow_tile(N, false), stream);
 }
 
 // Batched row-major GEMM  y[z][m][n] = sum_k x[z][m][k] * w[z][n][k]  (both operands K-contiguous rows with leading
@@ -1666,27 +1615,18 @@ extern "C" int nkb_gemm_batched(int dtype, const void* x, const void* w, void* y
         nkb_set_error("gemm_batched: K=%d must be a multiple of %d, ldx/ldw of %d, batch <= 65535", K, kte, 16 / esz);
         return 1;
     }
-    ConvParams p;
-    p.x = x; p.w = w; p.y = y; p.add = nullptr; p.bias = nullptr; p.stats = nullptr;
-    p.M = M; p.H = M; p.W = 1; p.Cin = K; p.ldx = ldx; p.P = M; p.Q = 1; p.Cout = N; p.ldy = ldy; p.ldadd = 0;
-    p.R = 1; p.S = 1; p.stride = 1; p.pad = 0; p.mode = 0; p.relu = 0; p.out_f32 = out_f32;
-    p.stride_w = 1; p.pad_w = 0; p.stem_cprw = 0;
-    p.divPQ = make_fastdiv((unsigned)M); p.divQ = make_fastdiv(1u);
-    p.add_h = 0; p.add_w = 0; p.act = 0; p.aux = nullptr; p.y2 = nullptr;
-    p.ldw = ldw; p.inner = inner; p.sxo = sxo; p.sxi = sxi; p.swo = swo; p.swi = swi; p.syo = syo; p.syi = syi;
+    ConvParams p = gemm_geometry(M, K, N, ldx, ldw, ldy);
+    p.x = x; p.w = w; p.y = y; p.out_f32 = out_f32;
+    p.inner = inner; p.sxo = sxo; p.sxi = sxi; p.swo = swo; p.swi = swi; p.syo = syo; p.syi = syi;
     // (profiler tag: the attention products are batched over (image, head); a split-K convolution calls with inner == 1)
     NkbProfScope prof(inner > 1 ? NKB_K_ATTN : NKB_K_CONV_FWD, stream, 2.0 * M * (double)N * K * outer * inner);
-    const bool narrow = N <= 64;
-    const int batch = outer * inner;
-    if (dtype == NKB_DT_BF16) return narrow ? launch_conv_auto<bf16_t, 64, 256>(p, stream, batch) : launch_conv_auto<bf16_t, 128, 128>(p, stream, batch);
-    return narrow ? launch_conv_auto<float, 64, 256>(p, stream, batch) : launch_conv_auto<float, 128, 128>(p, stream, batch);
+    return launch_conv<EPI_GENERAL>(p, dtype, narrow_tile(N, false), stream, outer * inner);
 }
 
 // number of row tiles the stats buffer must hold for a given launch: [tilesM][2][Cout] floats
 // (for the plain conv call: ldy == Cout, no residual, compute-dtype output)
 extern "C" int nkb_conv_gemm_stat_tiles(int dtype, int M, int Cout) {
-    static const int narrow_on = [] { const char* e = getenv("NKB_NARROW"); return e ? atoi(e) : 1; }();
-    const int tp = (Cout <= 64 && narrow_on) ? 256 : 128;
+    const int tp = narrow_tile(Cout) ? 256 : 128;
     return (M + tp - 1) / tp;
 }
 
@@ -1708,25 +1648,30 @@ static WgradPlan wgrad_plan(int esz, int M, int Cout, int Ntot, int target) {
     g.rows_per_split = rps;
     return g;
 }
-static thread_local int g_wgrad_target_override = 0;
-static int wgrad_target_wgs() {
-    // swept (128..768) on ResNet-50 and ViT-B/16: fewer splits = less competition with the main stream
-    constexpr int target_wgs = 256;
-    // (nkb_conv_wgrad_assign: a product the MAIN stream waits for — the Gram-form R = g^T a — fills the chip instead)
-    return g_wgrad_target_override > 0 ? g_wgrad_target_override : target_wgs;
+// workgroups the generic kernel's split aims at.  Swept (128..768) on ResNet-50 and ViT-B/16: fewer splits = less competition with
+// the main stream.  (nkb_conv_wgrad_assign's product is one the MAIN stream waits for — the Gram-form R = g^T a — and could fill the
+// chip instead; measured neutral on ResNet-50: 18.01 / 18.02 / 18.00 ms at 256 / 768 / 512, so it shares this target.)
+constexpr int WGRAD_TARGET_WGS = 256;
+
+// launches conv_wgrad_kernel from a filled parameter block
+static int launch_conv_wgrad(const WgradParams& p, int dtype, dim3 grid, hipStream_t stream, const char* name) {
+    const int TW = 256 / (dtype == NKB_DT_BF16 ? 2 : 4);
+    const int lds = 2 * 64 * 256 > (TW / 2) * (TW * 4 + 16) ? 2 * 64 * 256 : (TW / 2) * (TW * 4 + 16);
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipFuncSetAttribute((const void*)conv_wgrad_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+        hipFuncSetAttribute((const void*)conv_wgrad_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+        attr_set = true;
+    }
+    if (dtype == NKB_DT_BF16) hipLaunchKernelGGL(conv_wgrad_kernel<bf16_t>, grid, dim3(256), lds, stream, p);
+    else hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, dim3(256), lds, stream, p);
+    return nkb_check_launch(name);
 }
 
-// the generic split-over-pixels kernel's slabs (the larger of the two split counts a launch may take: the shared-GPU target, or
-// nkb_conv_wgrad_assign's full-chip one)
+// the generic split-over-pixels kernel's slabs
 static long long wgrad_generic_floats(int esz, int M, int Cin, int Cout, int R, int S, int has_bias) {
-    constexpr int main_wgs = 0;
-    long long need = 0;
-    for (int target : {wgrad_target_wgs(), main_wgs > 0 ? main_wgs : wgrad_target_wgs()}) {
-        const WgradPlan g = wgrad_plan(esz, M, Cout, R * S * Cin, target);
-        const long long n = (long long)g.splits * Cout * R * S * Cin + (has_bias ? (long long)g.splits * g.tilesN * Cout : 0);
-        if (n > need) need = n;
-    }
-    return need;
+    const WgradPlan g = wgrad_plan(esz, M, Cout, R * S * Cin, WGRAD_TARGET_WGS);
+    return (long long)g.splits * Cout * R * S * Cin + (has_bias ? (long long)g.splits * g.tilesN * Cout : 0);
 }
 // what the kernel nkb_conv_wgrad SELECTS for these operands (their real leading dimensions decide) needs
 static long long wgrad_selected_floats(int dtype, int N, int H, int W, int P, int Q, int Cin, int ldx, int Cout, int lddy, int R, int S,
@@ -1758,9 +1703,10 @@ extern "C" long long nkb_conv_wgrad_workspace_floats(int dtype, int N, int P, in
     return n > need ? n : need;
 }
 
-extern "C" int nkb_conv_wgrad(int dtype, const void* dy, const void* x, float* dw, float* dbias, int N, int H, int W,
-                              int Cin, int ldx, int P, int Q, int Cout, int lddy, int R, int S, int stride, int pad,
-                              float* workspace, long long workspace_floats, hipStream_t stream) {
+// dw (and dbias) += the product, or with assign: = the product (deterministic form only)
+static int conv_wgrad(bool assign, int dtype, const void* dy, const void* x, float* dw, float* dbias, int N, int H, int W,
+                      int Cin, int ldx, int P, int Q, int Cout, int lddy, int R, int S, int stride, int pad,
+                      float* workspace, long long workspace_floats, hipStream_t stream) {
     const int esz = dtype == NKB_DT_BF16 ? 2 : 4;
     const int epc = 16 / esz;
     if (dtype != NKB_DT_BF16 && dtype != NKB_DT_F32) { nkb_set_error("conv_wgrad: bad dtype %d", dtype); return 1; }
@@ -1783,76 +1729,58 @@ extern "C" int nkb_conv_wgrad(int dtype, const void* dy, const void* x, float* d
         // 3x3 / stride 1 / pad 1: the nine taps share one staged copy of the input (wgrad3x3.hip)
         NkbProfScope prof(NKB_K_CONV_WGRAD, stream, 2.0 * N * P * Q * (double)Cout * 9 * Cin,
                           ((double)N * H * W * Cin + (double)N * P * Q * Cout) * esz + 2.0 * 4.0 * Cout * 9 * Cin);
-        return nkb_launch_wgrad3x3(dy, x, dw, N, H, W, Cin, ldx, Cout, lddy, workspace, stream);
+        return nkb_launch_wgrad3x3(dy, x, dw, N, H, W, Cin, ldx, Cout, lddy, workspace, assign, stream);
     }
     if (nkb_wgradr_eligible(dtype, (long long)N * P * Q, Cin, Cout, R, S, stride, pad, ldx, lddy, dbias != nullptr)) {
         // 1x1 / stride 1 with channel counts in multiples of 256 and 128: 256 x 128 tiles streamed over the pixels (wgradr.hip)
         const long long M = (long long)N * P * Q;
         NkbProfScope prof(NKB_K_CONV_WGRAD, stream, 2.0 * M * (double)Cout * Cin,
                           ((double)M * Cin + (double)M * Cout) * esz + 2.0 * 4.0 * Cout * Cin);
-        return nkb_launch_wgradr(dy, x, dw, dbias, M, Cin, ldx, Cout, lddy, workspace, stream);
+        return nkb_launch_wgradr(dy, x, dw, dbias, M, Cin, ldx, Cout, lddy, workspace, assign, stream);
     }
     if (nkb_wgrad256_eligible(dtype, N * P * Q, Cin, Cout, R, S, stride, pad)) {
         // wide Linear layers: 256 x 256 tiles (wgrad256.hip)
         const int M = N * P * Q;
         NkbProfScope prof(NKB_K_CONV_WGRAD, stream, 2.0 * M * (double)Cout * Cin,
                           ((double)M * Cin + (double)M * Cout) * esz + 2.0 * 4.0 * Cout * Cin);
-        return nkb_launch_wgrad256(dy, x, dw, dbias, M, Cin, ldx, Cout, lddy, workspace, stream);
+        return nkb_launch_wgrad256(dy, x, dw, dbias, M, Cin, ldx, Cout, lddy, workspace, assign, stream);
     }
     WgradParams p;
     p.dy = dy; p.x = x; p.dw = dw; p.dbias = dbias;
     p.M = N * P * Q; p.H = H; p.W = W; p.Cin = Cin; p.ldx = ldx; p.P = P; p.Q = Q; p.Cout = Cout; p.lddy = lddy;
     p.R = R; p.S = S; p.stride = stride; p.pad = pad; p.Ntot = R * S * Cin;
     p.stride_w = stride; p.pad_w = pad;
-    const WgradPlan g = wgrad_plan(esz, p.M, Cout, p.Ntot, wgrad_target_wgs());
-    const int TW = g.TW;
-    p.tilesC = g.tilesC; p.tilesN = g.tilesN;
-    const int tiles = p.tilesC * p.tilesN;
-    const int splits = g.splits;
-    p.splits = splits; p.rows_per_split = g.rows_per_split;
+    const WgradPlan g = wgrad_plan(esz, p.M, Cout, p.Ntot, WGRAD_TARGET_WGS);
+    p.tilesC = g.tilesC; p.tilesN = g.tilesN; p.splits = g.splits; p.rows_per_split = g.rows_per_split;
     p.divPQ = make_fastdiv((unsigned)(P * Q)); p.divQ = make_fastdiv((unsigned)Q);
     p.divCin = make_fastdiv((unsigned)Cin); p.divS = make_fastdiv((unsigned)S);
-    p.out_t = nullptr; p.ldo = 0; p.inner = 1; p.sdo = p.sdi = p.sxo = p.sxi = p.soo = p.soi = 0;
     const long long slab = (long long)Cout * p.Ntot;
     if (workspace) {
         p.part = workspace; p.slab = slab;
-        p.bpart = dbias ? workspace + (size_t)splits * slab : nullptr;
-    }
-    const int lds = 2 * 64 * 256 > (TW / 2) * (TW * 4 + 16) ? 2 * 64 * 256 : (TW / 2) * (TW * 4 + 16);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)conv_wgrad_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-        hipFuncSetAttribute((const void*)conv_wgrad_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-        attr_set = true;
+        p.bpart = dbias ? workspace + (size_t)g.splits * slab : nullptr;
     }
     {
         NkbProfScope prof(NKB_K_CONV_WGRAD, stream, 2.0 * p.M * (double)Cout * p.Ntot,
                           ((double)N * H * W * Cin + (double)p.M * Cout) * esz + 2.0 * 4.0 * Cout * p.Ntot);
-        dim3 grid((unsigned)tiles * (unsigned)splits);
-        if (dtype == NKB_DT_BF16) hipLaunchKernelGGL(conv_wgrad_kernel<bf16_t>, grid, dim3(256), lds, stream, p);
-        else hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, dim3(256), lds, stream, p);
-        const int rc = nkb_check_launch("conv_wgrad");
+        const int rc = launch_conv_wgrad(p, dtype, dim3((unsigned)(g.tilesC * g.tilesN) * (unsigned)g.splits), stream, "conv_wgrad");
         if (rc || !workspace) return rc;
     }
-    NkbProfScope prof(NKB_K_WGRAD_REDUCE, stream, 0, 4.0 * ((double)splits + 2.0) * slab);
-    int rc = nkb_launch_wgrad_reduce(workspace, slab, splits, dw, slab, stream);
-    if (!rc && dbias) rc = nkb_launch_wgrad_reduce(p.bpart, Cout, splits * p.tilesN, dbias, Cout, stream);
+    NkbProfScope prof(NKB_K_WGRAD_REDUCE, stream, 0, 4.0 * ((double)g.splits + 2.0) * slab);
+    int rc = nkb_launch_wgrad_reduce(workspace, slab, g.splits, dw, slab, assign, stream);
+    if (!rc && dbias) rc = nkb_launch_wgrad_reduce(p.bpart, Cout, g.splits * p.tilesN, dbias, Cout, assign, stream);
     return rc;
 }
-
+extern "C" int nkb_conv_wgrad(int dtype, const void* dy, const void* x, float* dw, float* dbias, int N, int H, int W,
+                              int Cin, int ldx, int P, int Q, int Cout, int lddy, int R, int S, int stride, int pad,
+                              float* workspace, long long workspace_floats, hipStream_t stream) {
+    return conv_wgrad(false, dtype, dy, x, dw, dbias, N, H, W, Cin, ldx, P, Q, Cout, lddy, R, S, stride, pad, workspace, workspace_floats, stream);
+}
 // nkb_conv_wgrad with "=" instead of "+=": dw (and dbias) are OVERWRITTEN by the product — needs the deterministic form (workspace).
 extern "C" int nkb_conv_wgrad_assign(int dtype, const void* dy, const void* x, float* dw, float* dbias, int N, int H, int W,
                                      int Cin, int ldx, int P, int Q, int Cout, int lddy, int R, int S, int stride, int pad,
                                      float* workspace, long long workspace_floats, hipStream_t stream) {
     if (workspace == nullptr) { nkb_set_error("conv_wgrad_assign: needs the slab workspace (the atomic form can only accumulate)"); return 1; }
-    // (measured neutral on ResNet-50: 18.01 / 18.02 / 18.00 ms at 256 / 768 / 512 — default: the shared-GPU target)
-    constexpr int main_wgs = 0;
-    g_wgrad_assign = true;
-    g_wgrad_target_override = main_wgs;
-    const int rc = nkb_conv_wgrad(dtype, dy, x, dw, dbias, N, H, W, Cin, ldx, P, Q, Cout, lddy, R, S, stride, pad, workspace, workspace_floats, stream);
-    g_wgrad_assign = false;
-    g_wgrad_target_override = 0;
-    return rc;
+    return conv_wgrad(true, dtype, dy, x, dw, dbias, N, H, W, Cin, ldx, P, Q, Cout, lddy, R, S, stride, pad, workspace, workspace_floats, stream);
 }
 
 // Batched "transposed-A" GEMM  out[z][a][b] = sum_m A[z][m][a] * B[z][m][b]  (both operands m-major, e.g. attention
@@ -1868,30 +1796,18 @@ extern "C" int nkb_gemm_tn_batched(int dtype, const void* a, const void* b, void
         return 1;
     }
     WgradParams p;
-    p.dy = a; p.x = b; p.dw = nullptr; p.dbias = nullptr;
-    p.M = M; p.H = M; p.W = 1; p.Cin = Nb; p.ldx = ldb; p.P = M; p.Q = 1; p.Cout = Na; p.lddy = lda;
-    p.R = 1; p.S = 1; p.stride = 1; p.pad = 0; p.Ntot = Nb;
-    p.stride_w = 1; p.pad_w = 0;
+    p.dy = a; p.x = b;
+    p.M = M; p.H = M; p.W = 1; p.Cin = Nb; p.ldx = ldb; p.P = M; p.Q = 1; p.Cout = Na; p.lddy = lda; p.Ntot = Nb;
     const int TW = 256 / esz;
     p.tilesC = (Na + TW - 1) / TW; p.tilesN = (Nb + TW - 1) / TW;
     p.splits = 1; p.rows_per_split = (M + 63) / 64 * 64;
     p.divPQ = make_fastdiv((unsigned)M); p.divQ = make_fastdiv(1u);
     p.divCin = make_fastdiv((unsigned)Nb); p.divS = make_fastdiv(1u);
     p.out_t = out; p.ldo = ldo; p.inner = inner; p.sdo = sao; p.sdi = sai; p.sxo = sbo; p.sxi = sbi; p.soo = soo; p.soi = soi;
-    const int lds = 2 * 64 * 256 > (TW / 2) * (TW * 4 + 16) ? 2 * 64 * 256 : (TW / 2) * (TW * 4 + 16);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)conv_wgrad_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-        hipFuncSetAttribute((const void*)conv_wgrad_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-        attr_set = true;
-    }
     // (profiler tag: attention's dK / dV products are batched over (image, head); the Gram algebra's Q = V^T W is one product — VERDICT r4:
     // it showed up as `attention` in a ResNet-50 step)
     NkbProfScope prof(inner > 1 ? NKB_K_ATTN : NKB_K_MISC, stream, 2.0 * M * (double)Na * Nb * outer * inner);
-    dim3 grid((unsigned)(p.tilesC * p.tilesN), 1, (unsigned)(outer * inner));
-    if (dtype == NKB_DT_BF16) hipLaunchKernelGGL(conv_wgrad_kernel<bf16_t>, grid, dim3(256), lds, stream, p);
-    else hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, dim3(256), lds, stream, p);
-    return nkb_check_launch("gemm_tn_batched");
+    return launch_conv_wgrad(p, dtype, dim3((unsigned)(p.tilesC * p.tilesN), 1, (unsigned)(outer * inner)), stream, "gemm_tn_batched");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1926,19 +1842,12 @@ extern "C" int nkb_stem_conv(int dtype, const void* xp, const void* wp, void* y,
     }
     const StemGeom g = stem_geom(dtype, Wp);
     const int P = (H + 6 - 7) / 2 + 1, Q = (W + 6 - 7) / 2 + 1;
-    ConvParams p;
-    p.x = xp; p.w = wp; p.y = y; p.add = nullptr; p.bias = nullptr; p.stats = stats;
-    p.M = N * P * Q; p.H = H; p.W = g.Wc * g.rpt; p.Cin = 8 * g.epc; p.ldx = g.epc; p.P = P; p.Q = Q; p.Cout = Cout;
-    p.ldy = ldy; p.ldadd = 0; p.R = g.ktiles; p.S = 1; p.stride = 2; p.pad = 3; p.mode = 0; p.relu = 0; p.out_f32 = 0;
+    ConvParams p = conv_geometry(N, H, g.Wc * g.rpt, 8 * g.epc, g.epc, P, Q, Cout, ldy, g.ktiles, 1, 2, 3, 0);
     p.stride_w = g.stride_w; p.pad_w = g.pad_w; p.stem_cprw = g.cprw;
-    p.divPQ = make_fastdiv((unsigned)(P * Q)); p.divQ = make_fastdiv((unsigned)Q);
-    p.ldw = g.ktiles * 8 * g.epc; p.inner = 1; p.sxo = p.sxi = p.swo = p.swi = p.syo = p.syi = 0;
-    p.add_h = 0; p.add_w = 0; p.act = 0; p.aux = nullptr; p.y2 = nullptr;
+    p.x = xp; p.w = wp; p.y = y; p.stats = stats;
     NkbProfScope prof(NKB_K_CONV_FWD, stream, 2.0 * p.M * (double)Cout * 147,
                       ((double)N * H * Wp * 4 + (double)p.M * Cout) * (dtype == NKB_DT_BF16 ? 2 : 4));
-    const bool narrow = Cout <= 64;
-    if (dtype == NKB_DT_BF16) return narrow ? launch_conv_auto<bf16_t, 64, 256>(p, stream) : launch_conv_auto<bf16_t, 128, 128>(p, stream);
-    return narrow ? launch_conv_auto<float, 64, 256>(p, stream) : launch_conv_auto<float, 128, 128>(p, stream);
+    return launch_conv<EPI_GENERAL>(p, dtype, narrow_tile(Cout, false), stream);
 }
 
 // dwp[Cout][7*cprw*EPC] (fp32, caller-zeroed) += dY^T * window(xp); fold into the parameter gradient with nkb_stem_wfold
@@ -1964,7 +1873,7 @@ extern "C" int nkb_stem_wgrad(int dtype, const void* dy, const void* xp, float* 
     if (lddy % g.epc || lddy < (Cout + g.epc - 1) / g.epc * g.epc) { nkb_set_error("stem_wgrad: bad lddy=%d", lddy); return 1; }
     const int P = (H + 6 - 7) / 2 + 1, Q = (W + 6 - 7) / 2 + 1;
     WgradParams p;
-    p.dy = dy; p.x = xp; p.dw = dwp; p.dbias = nullptr;
+    p.dy = dy; p.x = xp; p.dw = dwp;
     p.M = N * P * Q; p.H = H; p.W = g.Wc; p.Cin = g.epc; p.ldx = g.epc; p.P = P; p.Q = Q; p.Cout = Cout; p.lddy = lddy;
     p.R = 7; p.S = g.cprw; p.stride = 2; p.pad = 3; p.stride_w = g.stride_w; p.pad_w = g.pad_w; p.Ntot = 7 * g.cprw * g.epc;
     const int TW = 256 / esz;
@@ -1980,22 +1889,11 @@ extern "C" int nkb_stem_wgrad(int dtype, const void* dy, const void* xp, float* 
     p.splits = splits; p.rows_per_split = rps;
     p.divPQ = make_fastdiv((unsigned)(P * Q)); p.divQ = make_fastdiv((unsigned)Q);
     p.divCin = make_fastdiv((unsigned)g.epc); p.divS = make_fastdiv((unsigned)g.cprw);
-    p.out_t = nullptr; p.ldo = 0; p.inner = 1; p.sdo = p.sdi = p.sxo = p.sxi = p.soo = p.soi = 0;
-    const int lds = 2 * 64 * 256 > (TW / 2) * (TW * 4 + 16) ? 2 * 64 * 256 : (TW / 2) * (TW * 4 + 16);
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipFuncSetAttribute((const void*)conv_wgrad_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-        hipFuncSetAttribute((const void*)conv_wgrad_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-        attr_set = true;
-    }
     {
         NkbProfScope prof(NKB_K_CONV_WGRAD, stream, 2.0 * p.M * (double)Cout * p.Ntot);
-        dim3 grid((unsigned)tiles * (unsigned)splits);
-        if (dtype == NKB_DT_BF16) hipLaunchKernelGGL(conv_wgrad_kernel<bf16_t>, grid, dim3(256), lds, stream, p);
-        else hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, dim3(256), lds, stream, p);
-        const int rc = nkb_check_launch("stem_wgrad");
+        const int rc = launch_conv_wgrad(p, dtype, dim3((unsigned)tiles * (unsigned)splits), stream, "stem_wgrad");
         if (rc || !workspace) return rc;
     }
     NkbProfScope prof(NKB_K_WGRAD_REDUCE, stream, 0, 4.0 * ((double)splits + 2.0) * p.slab);
-    return nkb_launch_wgrad_reduce(workspace, p.slab, splits, dwp, p.slab, stream);
+    return nkb_launch_wgrad_reduce(workspace, p.slab, splits, dwp, p.slab, /*assign=*/false, stream);
 }

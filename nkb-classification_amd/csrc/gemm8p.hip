@@ -1421,7 +1421,7 @@ extern "C" int nkb_gemm_fp8(int mode, const void* xq, const void* wq, void* y, c
         else hipLaunchKernelGGL((gemm8p_kernel<true, 2>), grid, dim3(512), lds, stream, p);
     }
     int rc_ = nkb_check_launch("gemm_fp8");
-    if (!rc_ && colsum) rc_ = nkb_launch_wgrad_reduce(colsum_work, N, M / 256, colsum, N, stream);
+    if (!rc_ && colsum) rc_ = nkb_launch_wgrad_reduce(colsum_work, N, M / 256, colsum, N, /*assign=*/false, stream);
     return rc_;
 }
 
@@ -1679,7 +1679,7 @@ extern "C" int nkb_fp8_quantize_colsum(int kind, const void* src, long long rows
                             (unsigned char*)nullptr, workspace, rpb, kind, row_scale, rps);
     const int rc = nkb_check_launch("fp8_quantize_colsum");
     if (rc) return rc;
-    return nkb_launch_wgrad_reduce(workspace, C, ry, colsum, C, stream);
+    return nkb_launch_wgrad_reduce(workspace, C, ry, colsum, C, /*assign=*/false, stream);
 }
 extern "C" int nkb_fp8_amax(int dtype, const void* src, long long n, float* state, hipStream_t stream) {
     if ((dtype != NKB_DT_BF16 && dtype != NKB_DT_F32) || n <= 0) { nkb_set_error("fp8_amax: dtype %d n %lld", dtype, n); return 1; }

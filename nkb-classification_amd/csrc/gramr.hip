@@ -11,7 +11,7 @@
 // (32 / 128 accumulator registers per lane); pixels stream through a ring of three LDS stages (32 KB of g + 8 KB of a each) by DMA, two
 // stages ahead; the contraction runs over the 32 pixels of an MFMA k-step with both operands through ds_read_b64_tr_b16 (rows of 512 /
 // 1024 / 128 / 256 bytes, their 32-byte channel blocks XOR-swizzled by the pixel on the DMA's source side: conflict-free, brute-forced);
-// every workgroup leaves ONE fp32 slab, summed in workgroup order (nkb_launch_wgrad_reduce_mode) — deterministic, no atomics.
+// every workgroup leaves ONE fp32 slab, summed in workgroup order (nkb_launch_wgrad_reduce) — deterministic, no atomics.
 #include "common.h"
 #include "convp.h"
 #include <type_traits>
@@ -237,5 +237,5 @@ extern "C" int nkb_gramr(int dtype, const void* g, int ldg, const void* a, int l
         if (int rc = nkb_check_launch("gramr")) return rc;
     }
     NkbProfScope prof(NKB_K_WGRAD_REDUCE, stream, 0, 4.0 * ((double)gg.nwg + 2.0) * co * ci);
-    return nkb_launch_wgrad_reduce_mode(workspace, (long long)co * ci, gg.nwg, R, (long long)co * ci, mode & 1, stream);
+    return nkb_launch_wgrad_reduce(workspace, (long long)co * ci, gg.nwg, R, (long long)co * ci, (mode & 1) != 0, stream);
 }

@@ -581,5 +581,5 @@ extern "C" int nkb_stemp_wgrad(int dtype, const void* dy, const void* xp, float*
         if (int rc = nkb_check_launch("stemp_wgrad")) return rc;
     }
     NkbProfScope prof(NKB_K_WGRAD_REDUCE, stream, 0, 4.0 * ((double)g.nwg + 2.0) * 64 * 224);
-    return nkb_launch_wgrad_reduce(workspace, 64ll * 224, g.nwg, dwp, 64ll * 224, stream);
+    return nkb_launch_wgrad_reduce(workspace, 64ll * 224, g.nwg, dwp, 64ll * 224, /*assign=*/false, stream);
 }

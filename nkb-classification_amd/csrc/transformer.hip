@@ -829,7 +829,7 @@ extern "C" int nkb_colsum2d(int dtype, const void* x, float* out, long long rows
     else hipLaunchKernelGGL(colsum2d_kernel<float>, grid, dim3(256), 0, stream, (const float*)x, out, rows, C, ld, rpb, workspace);
     const int rc = nkb_check_launch("colsum2d");
     if (rc || !workspace) return rc;
-    return nkb_launch_wgrad_reduce(workspace, C, ry, out, C, stream);
+    return nkb_launch_wgrad_reduce(workspace, C, ry, out, C, /*assign=*/false, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------

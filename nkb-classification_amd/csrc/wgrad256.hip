@@ -498,7 +498,7 @@ long long nkb_wgrad256_workspace_floats(int M, int Cin, int Cout, int has_bias) 
 }
 
 int nkb_launch_wgrad256(const void* dy, const void* x, float* dw, float* dbias, int M, int Cin, int ldx, int Cout, int lddy,
-                        float* workspace, hipStream_t stream) {
+                        float* workspace, bool assign, hipStream_t stream) {
     W256Params p;
     p.dy = (const bf16_t*)dy; p.x = (const bf16_t*)x; p.dw = dw; p.dbias = dbias;
     p.M = M; p.lddy = lddy; p.ldx = ldx; p.Ntot = Cin;
@@ -520,8 +520,8 @@ int nkb_launch_wgrad256(const void* dy, const void* x, float* dw, float* dbias, 
     hipLaunchKernelGGL(wgrad8p_kernel, dim3((unsigned)tiles * (unsigned)p.splits), dim3(512), lds, stream, p);
     int rc = nkb_check_launch("wgrad256");
     if (rc || !workspace) return rc;
-    rc = nkb_launch_wgrad_reduce(workspace, p.slab, p.splits, dw, p.slab, stream);
-    if (!rc && dbias) rc = nkb_launch_wgrad_reduce(p.bpart, Cout, p.splits, dbias, Cout, stream);
+    rc = nkb_launch_wgrad_reduce(workspace, p.slab, p.splits, dw, p.slab, assign, stream);
+    if (!rc && dbias) rc = nkb_launch_wgrad_reduce(p.bpart, Cout, p.splits, dbias, Cout, assign, stream);
     return rc;
 }
 
@@ -577,5 +577,5 @@ extern "C" int nkb_wgrad_fp8(const void* gq, const void* xq, float* dw, const fl
     hipLaunchKernelGGL(wgrad8f_kernel, dim3((unsigned)tiles * (unsigned)p.splits), dim3(512), lds, stream, p);
     int rc = nkb_check_launch("wgrad_fp8");
     if (rc) return rc;
-    return nkb_launch_wgrad_reduce(workspace, p.slab, p.splits, dw, p.slab, stream);
+    return nkb_launch_wgrad_reduce(workspace, p.slab, p.splits, dw, p.slab, /*assign=*/false, stream);
 }

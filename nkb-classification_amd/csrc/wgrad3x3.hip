@@ -318,7 +318,7 @@ long long nkb_wgrad3x3_workspace_floats(int N, int H, int W, int Cin, int Cout) 
 }
 
 int nkb_launch_wgrad3x3(const void* dy, const void* x, float* dw, int N, int H, int W, int Cin, int ldx, int Cout, int lddy,
-                        float* workspace, hipStream_t stream) {
+                        float* workspace, bool assign, hipStream_t stream) {
     nkb_count_launch(2);
     W3Params p;
     p.dy = (const bf16_t*)dy; p.x = (const bf16_t*)x; p.dw = dw; p.part = workspace;
@@ -337,5 +337,5 @@ int nkb_launch_wgrad3x3(const void* dy, const void* x, float* dw, int N, int H, 
     }
     int rc = nkb_check_launch("wgrad3x3");
     if (rc || !workspace) return rc;
-    return nkb_launch_wgrad_reduce(workspace, p.slab, p.splits, dw, p.slab, stream);
+    return nkb_launch_wgrad_reduce(workspace, p.slab, p.splits, dw, p.slab, assign, stream);
 }

@@ -321,7 +321,7 @@ long long nkb_wgradr_workspace_floats(long long M, int Cin, int Cout, int has_bi
 }
 
 int nkb_launch_wgradr(const void* dy, const void* x, float* dw, float* dbias, long long M, int Cin, int ldx, int Cout, int lddy,
-                      float* workspace, hipStream_t stream) {
+                      float* workspace, bool assign, hipStream_t stream) {
     WRPlan g;
     if (!wr_plan(M, Cin, Cout, dbias != nullptr, g)) { nkb_set_error("wgradr: shape not eligible (M=%lld Cin=%d Cout=%d)", M, Cin, Cout); return 1; }
     nkb_count_launch(10);
@@ -335,6 +335,6 @@ int nkb_launch_wgradr(const void* dy, const void* x, float* dw, float* dbias, lo
     if (g.wide) wr_launch<2, 8>(p, stream); else wr_launch<3, 4>(p, stream);
     int rc = nkb_check_launch("wgradr");
     if (rc || !workspace) return rc;
-    if (dbias) return nkb_launch_wgrad_reduce2(workspace, p.slab, g.splits, dw, p.slab, p.bpart, Cout, dbias, Cout, stream);
-    return nkb_launch_wgrad_reduce(workspace, p.slab, g.splits, dw, p.slab, stream);
+    if (dbias) return nkb_launch_wgrad_reduce2(workspace, p.slab, g.splits, dw, p.slab, p.bpart, Cout, dbias, Cout, assign, stream);
+    return nkb_launch_wgrad_reduce(workspace, p.slab, g.splits, dw, p.slab, assign, stream);
 }
