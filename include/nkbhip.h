@@ -36,7 +36,7 @@ int nkb_version(void);
 /* Launch counters of the specialised kernels since process start (or the last reset): which = 0 eight-phase GEMM (gemm8p), 1 eight-phase
  * weight gradient (wgrad8p / wgrad256), 2 shared-strip 3x3 weight gradient, 3 fp8 weight gradient, 4 Gram-form closing convolution,
  * 5 bn_apply fused with the Gram matrix, 6 row-balanced 3x3 core (convp), 7 pixel-resident 1x1 expansion (conv1p), 8 ring-buffered stem
- * (stemp: forward and weight gradient), 9 streamed g^T a (gramr), 10 row-streaming 256 x 128-tile 1x1 weight gradient (wgradr).  Tests use them to prove that a benchmark configuration took the path it is priced on. */
+ * (stemp: forward and weight gradient), 9 streamed g^T a (gramr), 10 row-streaming 256 x 128-tile 1x1 weight gradient (wgradr), 13 depthwise convolution (dwconv: forward, data and weight gradient), 14 layer scale.  Tests use them to prove that a benchmark configuration took the path it is priced on. */
 long long nkb_kernel_launches(int which, int reset);
 
 /* Implicit-GEMM convolution / linear layer on MFMA.
@@ -507,6 +507,30 @@ void nkb_prof_enable(int on);
 int nkb_prof_collect(double* ms, long long* launches, double* work, double* bytes, int slots);
 int nkb_prof_collect_raw(int* kernel_id, double* ms, double* work, double* bytes, int cap);
 const char* nkb_kernel_name(int kernel_id);
+
+/* Depthwise 7x7 convolution, stride 1, pad 3, NHWC (csrc/dwconv.hip): the `conv_dw` of a ConvNeXt block, which the reference reaches
+ * through timm.create_model("convnext_*", num_classes=0) at nkb_classification/model.py:82.
+ *   forward (dgrad = 0):  y[n,p,q,c] = bias[c] + sum_{r,s} w[c][r][s] * x[n, p+r-pad, q+s-pad, c]
+ *   data gradient (1):    the same kernel with the taps read back to front (w[c][R-1-r][R-1-s]) and no bias (pass NULL)
+ * add (optional, same shape and stride as y): y += add[n,p,q,c] at the store (the residual path's gradient in a block's backward).
+ * fp32 accumulation, output in the compute dtype.  w / bias are the fp32 MASTER parameters ([C][R][R] = the arena's [Cout][R][S][Cin]
+ * layout with Cin = 1, the order of conv_dw.weight): there is no bf16 shadow of a depthwise filter.  C % 64 == 0 (lanes are channels);
+ * any H, W >= 1; pixel strides ldx, ldy >= C; N*H*W*ld < 2^31; R = 7, pad = 3. */
+int nkb_dwconv(int dtype, int dgrad, const void* x, const float* w, const float* bias, const void* add, void* y, int N, int H, int W,
+               int C, int ldx, int ldy, int R, int pad, nkb_stream_t stream);
+/* dw[c][r][s] += sum_{n,p,q} g[n,p,q,c] * x[n, p+r-pad, q+s-pad, c] and (optional) dbias[c] += sum g, from one pass: every wave leaves
+ * its 50 sums per channel in a slab of `workspace`, and the slabs are added in a fixed order (no float atomics; two launches give the
+ * same bits).  workspace: at least nkb_dwconv_wgrad_workspace_floats(...) floats. */
+int nkb_dwconv_wgrad(int dtype, const void* g, const void* x, float* dw, float* dbias, int N, int H, int W, int C, int ldg, int ldx,
+                     int R, int pad, float* workspace, long long workspace_floats, nkb_stream_t stream);
+long long nkb_dwconv_wgrad_workspace_floats(int dtype, int N, int H, int W, int C, int R);
+/* Layer scale of the ConvNeXt block (the same call site).  forward (backward = 0): out[m][c] = a[m][c] + gamma[c] * z[m][c] (a: the
+ * residual, optional); backward: out[m][c] = gamma[c] * a[m][c] with a the incoming gradient, and (dgamma given) dgamma[c] +=
+ * sum_m a[m][c] * z[m][c] through per-block partial rows in `workspace` (nkb_layer_scale_workspace_floats) and an ordered sum.
+ * Packed rows of C % 64 == 0 elements, 16-byte aligned; rows * C < 2^31. */
+int nkb_layer_scale(int dtype, int backward, const void* z, const void* a, const float* gamma, void* out, float* dgamma, long long rows,
+                    int C, float* workspace, long long workspace_floats, nkb_stream_t stream);
+long long nkb_layer_scale_workspace_floats(long long rows, int C);
 
 #ifdef __cplusplus
 }

@@ -123,5 +123,6 @@ struct NkbProfScope {
 enum NkbKernelId {
     NKB_K_CONV_FWD = 0, NKB_K_CONV_DGRAD, NKB_K_CONV_WGRAD, NKB_K_BN_APPLY, NKB_K_BN_BWD_REDUCE, NKB_K_BN_BWD_APPLY,
     NKB_K_BN_FINALIZE, NKB_K_MAXPOOL, NKB_K_AVGPOOL, NKB_K_IM2COL, NKB_K_WPREP, NKB_K_LOSS, NKB_K_OPTIM, NKB_K_MISC,
-    NKB_K_LN, NKB_K_ATTN, NKB_K_GELU, NKB_K_WGRAD_REDUCE, NKB_K_COUNT
+    NKB_K_LN, NKB_K_ATTN, NKB_K_GELU, NKB_K_WGRAD_REDUCE, NKB_K_DWCONV_FWD, NKB_K_DWCONV_DGRAD, NKB_K_DWCONV_WGRAD,
+    NKB_K_LAYER_SCALE, NKB_K_COUNT
 };

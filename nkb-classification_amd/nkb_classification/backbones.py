@@ -275,6 +275,9 @@ def create_backbone(name: str, pretrained: bool = False) -> nn.Module:
     from .vit import create_vit
     m = create_vit(key)
     if m is None:
+        from .convnext import _CONVNEXTS, create_convnext
+        m = create_convnext(key)
+    if m is None:
         raise NotImplementedError(f"backbone {name!r} is not implemented by the HIP engine "
-                                  f"(available: {sorted(_RESNETS)} + vit_{{small,base,large}}_patch16_224)")
+                                  f"(available: {sorted(_RESNETS)} + vit_{{small,base,large}}_patch16_224 + {sorted(_CONVNEXTS)})")
     return m

@@ -1,0 +1,216 @@
+"""timm ConvNeXt family (convnext_base layout, num_classes=0) for the HIP engine: parameter containers with timm's state-dict
+names + the forward / backward execution plan.
+
+Reference call site: timm.create_model("convnext_base", ...) at /root/reference/nkb_classification/model.py:82 (the
+reference's configs/trtconfig.py trains this member).  The architecture is restated from memory, parity unpinned: timm is
+not available offline, so the layout below (stem 4x4/s4 conv + LayerNorm; per stage a LayerNorm + 2x2/s2 conv downsample
+and blocks of depthwise 7x7 conv -> LayerNorm -> Linear(C, 4C) -> exact-erf GELU -> Linear(4C, C) -> gamma -> residual; head
+LayerNorm of the global average pool; LayerNorm eps 1e-6; layer-scale init 1e-6) is pinned against a twin of our own
+(tests/convnext_reference.py), not against timm.  Cross-check: 342 tensors / 87 566 464 elements for convnext_base, which
+is timm's published 88 591 464 for the 1000-class model minus its 1 025 000-element fc.
+
+Activations stay [N*H*W, C] rows (NHWC) throughout, so the Linear / LayerNorm / GELU / dropout steps are the ViT's; the new
+HIP of this family is the depthwise convolution and the layer scale (csrc/dwconv.hip).
+"""
+from __future__ import annotations
+
+import torch
+from torch import nn
+
+from . import hip
+from .backbones import _ParamOnly
+from .hipnet import HipEngine
+
+_GELU_KEEP_DERIV = True   # forward stores gelu'(pre); backward = fc2-dgrad epilogue multiply (as vit.py)
+
+
+class _Mlp(_ParamOnly):
+    def __init__(self, dim, hidden):
+        super().__init__()
+        self.fc1 = nn.Linear(dim, hidden)
+        self.drop1 = nn.Dropout(0.0)
+        self.fc2 = nn.Linear(hidden, dim)
+        self.drop2 = nn.Dropout(0.0)
+
+
+class _Block(_ParamOnly):
+    def __init__(self, dim, ls_init=1e-6):
+        super().__init__()
+        self.conv_dw = nn.Conv2d(dim, dim, 7, padding=3, groups=dim)
+        self.norm = nn.LayerNorm(dim, eps=1e-6)
+        self.mlp = _Mlp(dim, 4 * dim)
+        self.gamma = nn.Parameter(ls_init * torch.ones(dim))
+
+
+class _Stage(_ParamOnly):
+    def __init__(self, in_dim, dim, depth, downsample):
+        super().__init__()
+        if downsample:
+            self.downsample = nn.Sequential(nn.LayerNorm(in_dim, eps=1e-6), nn.Conv2d(in_dim, dim, 2, 2))
+        else:
+            self.downsample = nn.Identity()
+        self.blocks = nn.Sequential(*[_Block(dim) for _ in range(depth)])
+
+
+class _Head(_ParamOnly):
+    def __init__(self, dim):
+        super().__init__()
+        self.norm = nn.LayerNorm(dim, eps=1e-6)
+        self.drop = nn.Dropout(0.0)
+
+
+class HipConvNeXt(_ParamOnly):
+    family = "convnext"
+
+    def __init__(self, depths=(3, 3, 27, 3), dims=(128, 256, 512, 1024)):
+        super().__init__()
+        self.depths, self.dims = tuple(depths), tuple(dims)
+        self.num_features = dims[-1]
+        self.stem = nn.Sequential(nn.Conv2d(3, dims[0], 4, 4), nn.LayerNorm(dims[0], eps=1e-6))
+        self.stages = nn.Sequential(*[_Stage(dims[max(i - 1, 0)], dims[i], depths[i], i > 0) for i in range(len(dims))])
+        self.head = _Head(dims[-1])
+        for m in self.modules():
+            if isinstance(m, (nn.Conv2d, nn.Linear)):
+                nn.init.trunc_normal_(m.weight, std=0.02)
+                nn.init.zeros_(m.bias)
+
+    def gemm_convs(self):
+        """The Linear layers and the three 2x2 / stride-2 downsample convolutions (generic implicit-GEMM kernels); the depthwise
+        filters are read as fp32 masters by their own kernel and need no weight preparation."""
+        out = [m for m in self.modules() if isinstance(m, nn.Linear)]
+        out += [st.downsample[1] for st in self.stages if not isinstance(st.downsample, nn.Identity)]
+        return out
+
+    def stem_convs(self):
+        return [self.stem[0]]
+
+    def fp8_linears(self):
+        """fp8 contractions are out of scope for this family, so cfg.amp_dtype = "fp8" runs it in bf16.  The empty list is what says
+        so: a backbone WITHOUT this method leaves HipEngine.fp8_candidates at None, and the engine then takes every registered
+        2-D weight (gemm_convs(): this family's Linear layers) as an fp8 candidate."""
+        return []
+
+    # ---- execution plan ---------------------------------------------------------------
+    def run_forward(self, eng: HipEngine, img: torch.Tensor, train: bool) -> torch.Tensor:
+        """Dropout sites are the nn.Dropout children the reference's set_dropout rewrites (model.py:66-72): mlp.drop1 after the
+        GELU, mlp.drop2 before the layer scale, head.drop on the embedding.  Stochastic depth is off (drop_path_rate = 0)."""
+        for k in [k for k in eng.saved if k.endswith("_drop")]:
+            del eng.saved[k]                                 # masks of a previous step must not leak into this backward
+        B, Cin, Hh, Ww = img.shape
+        cv, a = self.stem[0], eng.arena
+        ps = cv.kernel_size[0]
+        H, W = Hh // ps, Ww // ps
+        if H < 8 or W < 8:
+            raise RuntimeError(f"ConvNeXt needs images of at least {8 * ps}x{8 * ps} (three 2x2 downsamples), got {Hh}x{Ww}")
+        D0 = self.dims[0]
+        K = Cin * ps * ps
+        kp = eng.kpad(K)
+        col = eng.ws.get("stem.col", (B * H * W, kp), eng.T)
+        hip.im2row(eng.d, img, col, B, Cin, Hh, Ww, ps, ps, ps, 0, kp)
+        tok = eng.ws.get("stem.tok", (B * H * W, D0), eng.T)
+        hip.conv_gemm(eng.d, 0, col, eng.w_fwd(cv.weight), tok, N=B * H * W, H=1, W=1, Cin=kp, ldx=kp, P=1, Q=1, Cout=D0, ldy=D0,
+                      bias=a.param_flat(cv.bias))
+        if train:
+            eng.saved["stem"] = dict(col=col, B=B, H=H, W=W, kp=kp, K=K)
+        x = eng.layernorm("stem.ln", tok, self.stem[1], train)
+        for si, st in enumerate(self.stages):
+            C = self.dims[si]
+            if si > 0:
+                h = eng.layernorm(f"s{si}.ds.ln", x, st.downsample[0], train)
+                y = eng.conv_bias(f"s{si}.ds", h.view(B, H, W, self.dims[si - 1]), st.downsample[1], train)
+                H, W = y.shape[1], y.shape[2]
+                x = y.view(B * H * W, C)
+            for bi, blk in enumerate(st.blocks):
+                k, mlp = f"s{si}.b{bi}", blk.mlp
+                y = eng.dwconv(f"{k}.dw", x, blk.conv_dw, B, H, W, train)
+                h = eng.layernorm(f"{k}.ln", y, blk.norm, train)
+                keep = _GELU_KEEP_DERIV and not (train and mlp.drop1.p > 0)
+                u = eng.linear_gelu_keep_derivative(f"{k}.fc1", f"{k}.act", h, mlp.fc1, train) if keep else None
+                if u is None:
+                    u = eng.gelu(f"{k}.act", eng.linear(f"{k}.fc1", h, mlp.fc1, train), train, keep_derivative=keep)
+                u = eng.dropout(f"{k}.mlp_drop", u, mlp.drop1.p, train)
+                z = eng.linear(f"{k}.fc2", u, mlp.fc2, train)
+                z = eng.dropout(f"{k}.mlp2_drop", z, mlp.drop2.p, train)
+                x = eng.layer_scale(f"{k}.ls", z, blk.gamma, x, train)
+        pooled = eng.avgpool("gap", x.view(B, H, W, self.dims[-1]))
+        emb = eng.layernorm("head.ln", pooled, self.head.norm, train)
+        return eng.dropout("head_drop", emb, self.head.drop.p, train)
+
+    def run_backward(self, eng: HipEngine, g_emb: torch.Tensor, on_done=None):
+        """on_done(module) is called as soon as every parameter gradient of `module` (head norm, stages 3 .. 0, stem) is final,
+        so the data-parallel reducer can start exchanging it while backward continues."""
+        sv = eng.saved["stem"]
+        B = sv["B"]
+        a = eng.arena
+        D = self.dims[-1]
+        g_emb = eng.dropout_backward("head_drop", g_emb, "gemb")
+        gp = eng.layernorm_backward("head.ln", g_emb, eng.scratch("gpool", (B, D)), D)
+        gx = eng.avgpool_backward("gap", gp, "g0")
+        gx = gx.view(-1, D)
+        if on_done is not None:
+            on_done(self.head)
+        # one unit per block or downsample: begin_block gives consecutive units scratch sets of opposite parity, so a unit's output
+        # ("gx") never aliases its input (the previous unit's "gx") nor what the side-stream work of the unit before still reads
+        unit = sum(self.depths) + len(self.dims) - 1
+        for si in range(len(self.stages) - 1, -1, -1):
+            st, C = self.stages[si], self.dims[si]
+            M = gx.shape[0]
+            for bi in range(len(st.blocks) - 1, -1, -1):
+                unit -= 1
+                eng.begin_block(unit)
+                k = f"s{si}.b{bi}"
+                gz = eng.layer_scale_backward(f"{k}.ls", gx, "gz")             # branch gradient; the residual path keeps gx
+                g2 = eng.dropout_backward(f"{k}.mlp2_drop", gz, "g2")
+                if "gp" in eng.saved[f"{k}.act"]:
+                    d_a = eng.linear_backward_through_saved_derivative(f"{k}.fc2", f"{k}.act", g2, "da")
+                else:
+                    d_u = eng.dropout_backward(f"{k}.mlp_drop", eng.linear_backward(f"{k}.fc2", g2, "du"), "du2")
+                    d_a = eng.gelu_backward(f"{k}.act", d_u, "da")
+                d_h = eng.linear_backward(f"{k}.fc1", d_a, "dh")
+                gy = eng.layernorm_backward(f"{k}.ln", d_h, eng.scratch("gy", (M, C)), C)
+                gx = eng.dwconv_backward(f"{k}.dw", gy, "gx", add=gx)
+                eng.end_block(unit)
+            if si > 0:
+                unit -= 1
+                eng.begin_block(unit)
+                gsv = eng.saved[f"s{si}.ds"]["geom"]
+                gh = eng.conv_bias_backward(f"s{si}.ds", gx.view(B, gsv["P"], gsv["Q"], C), "gds")
+                Cp = self.dims[si - 1]
+                gx = eng.layernorm_backward(f"s{si}.ds.ln", gh.view(-1, Cp), eng.scratch("gx", (gh.numel() // Cp, Cp)), Cp)
+                eng.end_block(unit)
+            if on_done is not None:
+                on_done(st)
+        eng.begin_block(-1)
+        D0, rows = self.dims[0], sv["B"] * sv["H"] * sv["W"]
+        d_tok = eng.layernorm_backward("stem.ln", gx, eng.scratch("dtok", (rows, D0)), D0)
+        cv = self.stem[0]
+        kp, K = sv["kp"], sv["K"]
+        if kp == K:
+            eng.wgrad(d_tok, sv["col"], a.grad_flat(cv.weight), N=rows, H=1, W=1, Cin=kp, ldx=kp, P=1, Q=1, Cout=D0, lddy=D0,
+                      dbias=a.grad_flat(cv.bias))
+        else:
+            dwp = eng.ws.get("stem.dwpad", (D0, kp), torch.float32)
+            hip.zero_(dwp)
+            eng.wgrad(d_tok, sv["col"], dwp, N=rows, H=1, W=1, Cin=kp, ldx=kp, P=1, Q=1, Cout=D0, lddy=D0)
+            hip.add2d(dwp, a.grad_flat(cv.weight), D0, K, kp, K)
+            eng.colsum2d(d_tok, a.grad_flat(cv.bias), rows, D0, D0)
+        if on_done is not None:
+            on_done(self.stem)
+
+
+_CONVNEXTS = {
+    "convnext_base": dict(depths=(3, 3, 27, 3), dims=(128, 256, 512, 1024)),
+    "convnext_test": dict(depths=(1, 1, 2, 1), dims=(128, 128, 256, 256)),   # reduced member for fast parity tests
+}
+# members whose widths nkb_layernorm (D % 128 == 0, D <= 2048) does not take yet
+_CONVNEXTS_UNSUPPORTED = {
+    "convnext_tiny": (96, 192, 384, 768), "convnext_small": (96, 192, 384, 768), "convnext_large": (192, 384, 768, 1536),
+}
+
+
+def create_convnext(name: str):
+    if name in _CONVNEXTS_UNSUPPORTED:
+        raise NotImplementedError(f"backbone {name!r}: widths {_CONVNEXTS_UNSUPPORTED[name]} are not all multiples of 128, which the "
+                                  f"LayerNorm kernel of the HIP engine needs (available ConvNeXt members: {sorted(_CONVNEXTS)})")
+    cfg = _CONVNEXTS.get(name)
+    return HipConvNeXt(**cfg) if cfg else None

@@ -125,6 +125,11 @@ _SIGS = {
     "nkb_wgrad_fp8_workspace_floats": (i64, [i32, i32, i32]),
     "nkb_wgrad_fp8": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp]),
     "nkb_gemm_fp8": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp] + [i32] * 8 + [vp]),
+    "nkb_dwconv": (i32, [i32, i32, vp, vp, vp, vp, vp] + [i32] * 8 + [vp]),
+    "nkb_dwconv_wgrad": (i32, [i32, vp, vp, vp, vp] + [i32] * 8 + [vp, i64, vp]),
+    "nkb_dwconv_wgrad_workspace_floats": (i64, [i32] * 6),
+    "nkb_layer_scale": (i32, [i32, i32, vp, vp, vp, vp, vp, i64, i32, vp, i64, vp]),
+    "nkb_layer_scale_workspace_floats": (i64, [i64, i32]),
     "nkb_prof_enable": (None, [i32]),
     "nkb_prof_collect": (i32, [vp, vp, vp, vp, i32]),
     "nkb_prof_collect_raw": (i32, [vp, vp, vp, vp, i32]),
@@ -182,7 +187,8 @@ _PURE = frozenset({"nkb_kernel_launches", "nkb_linear_gelu_fused_ok", "nkb_versi
                    "nkb_bn_relu_maxpool_workspace_floats", "nkb_layernorm_workspace_floats", "nkb_loss_row_state_bytes",
                    "nkb_conv_wgrad_workspace_floats", "nkb_stem_wgrad_workspace_floats", "nkb_kernel_name",
                    "nkb_prof_enable", "nkb_prof_collect", "nkb_prof_collect_raw", "nkb_gemm8p_config", "nkb_gemm8p_ragged", "nkb_convp_config", "nkb_rowres_reserve_cus", "nkb_rowres_reserved_cus",
-                   "nkb_fp8_job_blocks", "nkb_wgrad_fp8_workspace_floats",
+                   "nkb_fp8_job_blocks", "nkb_wgrad_fp8_workspace_floats", "nkb_dwconv_wgrad_workspace_floats",
+                   "nkb_layer_scale_workspace_floats",
                    "nkb_fp8_quantize_colsum_workspace_floats",
                    "nkb_gram_bn_backward_workspace_floats", "nkb_bn_apply_gram_workspace_floats",
                    "nkb_plan_fn_count", "nkb_plan_fn_name", "nkb_plan_fn_args", "nkb_plan_max_args", "nkb_plan_entry_bytes",
@@ -443,9 +449,10 @@ def _device_allocs() -> int:
 
 def kernel_launches(which: str, reset: bool = False) -> int:
     """Launch count of a specialised kernel family: gemm8p, wgrad8p, wgrad3x3, wgrad8f, gram_conv, gram_bn_apply, convp, conv1p, stemp, gramr,
-    wgradr, gemm8p_ragged (the ragged-row companion of a gemm8p launch), gemm_fp8 (the fp8 forms of the gemm8p core)."""
+    wgradr, gemm8p_ragged (the ragged-row companion of a gemm8p launch), gemm_fp8 (the fp8 forms of the gemm8p core), dwconv (depthwise
+    convolution: forward, data and weight gradient), layer_scale."""
     idx = {"gemm8p": 0, "wgrad8p": 1, "wgrad3x3": 2, "wgrad8f": 3, "gram_conv": 4, "gram_bn_apply": 5, "convp": 6, "conv1p": 7,
-           "stemp": 8, "gramr": 9, "wgradr": 10, "gemm8p_ragged": 11, "gemm_fp8": 12}[which]
+           "stemp": 8, "gramr": 9, "wgradr": 10, "gemm8p_ragged": 11, "gemm_fp8": 12, "dwconv": 13, "layer_scale": 14}[which]
     return int(load().nkb_kernel_launches(idx, int(reset)))
 
 
@@ -1032,3 +1039,29 @@ def linear_residual_scaled(dtype, x, w, bias, add, row_scale, rows_per_sample, y
 def linear_gelu(dtype, act, x, w, bias, aux, y, y2, M, K, N):
     check(load().nkb_linear_gelu(dtype, act, ptr(x), ptr(w), ptr(bias), ptr(aux), ptr(y), ptr(y2), M, K, N, stream()),
           "linear_gelu")
+
+
+# ---- ConvNeXt: depthwise 7x7 convolution and layer scale (csrc/dwconv.hip) ------------------------
+def dwconv(dtype, x, w, bias, y, *, N, H, W, C, ldx, ldy, R=7, pad=3, dgrad=False, add=None):
+    """y = depthwise conv(x) + bias (+ add); dgrad: the data gradient (taps flipped, bias must be None).  w / bias: fp32 masters."""
+    check(load().nkb_dwconv(dtype, int(dgrad), ptr(x), ptr(w), ptr(bias), ptr(add), ptr(y), N, H, W, C, ldx, ldy, R, pad, stream()), "dwconv")
+
+
+def dwconv_wgrad_workspace(dtype, N, H, W, C, R=7) -> int:
+    return int(load().nkb_dwconv_wgrad_workspace_floats(dtype, N, H, W, C, R))
+
+
+def dwconv_wgrad(dtype, g, x, dw, dbias, *, N, H, W, C, ldg, ldx, workspace, R=7, pad=3):
+    """dw += g (*) x, dbias += sum g through per-wave slabs and an ordered sum (bit-identical across launches)."""
+    check(load().nkb_dwconv_wgrad(dtype, ptr(g), ptr(x), ptr(dw), ptr(dbias), N, H, W, C, ldg, ldx, R, pad, ptr(workspace),
+                                  workspace.numel() if workspace is not None else 0, stream()), "dwconv_wgrad")
+
+
+def layer_scale_workspace(rows, C_) -> int:
+    return int(load().nkb_layer_scale_workspace_floats(rows, C_))
+
+
+def layer_scale(dtype, backward, z, a, gamma, out, rows, C_, dgamma=None, workspace=None):
+    """forward: out = a + gamma * z; backward: out = gamma * a (a: incoming gradient), dgamma += sum_m a * z."""
+    check(load().nkb_layer_scale(dtype, int(backward), ptr(z), ptr(a), ptr(gamma), ptr(out), ptr(dgamma), rows, C_, ptr(workspace),
+                                 workspace.numel() if workspace is not None else 0, stream()), "layer_scale")

@@ -1467,3 +1467,76 @@ class HipEngine:
         hip.gemm_batched(self.d, dS, Kt, dqkv, T, dh, Tp, Tp, Tp, 3 * D, B, H, sp, (H * dh * Tp, dh * Tp), sq)
         hip.gemm_tn_batched(self.d, dS, q, dqkv[:, D:], T, T, dh, Tp, 3 * D, 3 * D, B, H, sp, sq, sq)
         return dqkv
+
+    # ------------------------------------------------------------------ ConvNeXt ops ----
+    def dwconv(self, key: str, x: torch.Tensor, conv: nn.Conv2d, N: int, H: int, W: int, train: bool) -> torch.Tensor:
+        """Depthwise 7x7 convolution (csrc/dwconv.hip) over [N*H*W, C] rows; filter and bias are read as fp32 masters straight from
+        the arena ([C][49], the order of conv_dw.weight): no bf16 shadow, no weight-prep job."""
+        C = conv.weight.shape[0]
+        a = self.arena
+        y = self.ws.get(key + ".y", (N * H * W, C), self.T)
+        hip.dwconv(self.d, x, a.param_flat(conv.weight), a.param_flat(conv.bias) if conv.bias is not None else None, y,
+                   N=N, H=H, W=W, C=C, ldx=C, ldy=C, R=conv.kernel_size[0], pad=conv.padding[0])
+        if train:
+            self.saved[key] = dict(x=x, conv=conv, geom=(N, H, W, C))
+        return y
+
+    def dwconv_backward(self, key: str, g: torch.Tensor, slot: Optional[str], add: Optional[torch.Tensor] = None):
+        """Weight / bias gradient on the side stream (slabs + ordered sum); data gradient (+ add, the residual path's gradient)
+        on the main stream: the forward kernel with the taps flipped."""
+        sv = self.saved[key]
+        conv, (N, H, W, C) = sv["conv"], sv["geom"]
+        a = self.arena
+        R, pad = conv.kernel_size[0], conv.padding[0]
+
+        def wgrad():
+            work = self.ws.at_least("wgrad.slabs." + self._stream_tag(), hip.dwconv_wgrad_workspace(self.d, N, H, W, C, R), torch.float32)
+            hip.dwconv_wgrad(self.d, g, sv["x"], a.grad_flat(conv.weight), a.grad_flat(conv.bias) if conv.bias is not None else None,
+                             N=N, H=H, W=W, C=C, ldg=C, ldx=C, workspace=work, R=R, pad=pad)
+        self.on_side(wgrad)
+        if slot is None:
+            return None
+        dx = self.scratch(slot, (N * H * W, C))
+        hip.dwconv(self.d, g, a.param_flat(conv.weight), None, dx, N=N, H=H, W=W, C=C, ldx=C, ldy=C, R=R, pad=pad, dgrad=True, add=add)
+        return dx
+
+    def layer_scale(self, key: str, z: torch.Tensor, gamma: nn.Parameter, add: torch.Tensor, train: bool) -> torch.Tensor:
+        """y = add + gamma[c] * z (the ConvNeXt block's per-channel scale and residual in one pass); z is kept for dgamma."""
+        M, C = z.shape
+        y = self.ws.get(key + ".y", (M, C), self.T)
+        hip.layer_scale(self.d, False, z, add, self.arena.param_flat(gamma), y, M, C)
+        if train:
+            self.saved[key] = dict(z=z, gamma=gamma)
+        return y
+
+    def layer_scale_backward(self, key: str, g: torch.Tensor, slot: str) -> torch.Tensor:
+        """gz = gamma[c] * g; dgamma[c] += sum_m g * z (per-block partial rows + ordered sum)."""
+        sv = self.saved[key]
+        z, gamma = sv["z"], sv["gamma"]
+        M, C = z.shape
+        work = self.ws.at_least("ls.part." + self._stream_tag(), hip.layer_scale_workspace(M, C), torch.float32)
+        gz = self.scratch(slot, (M, C))
+        hip.layer_scale(self.d, True, z, g, self.arena.param_flat(gamma), gz, M, C, dgamma=self.arena.grad_flat(gamma), workspace=work)
+        return gz
+
+    def conv_bias(self, key: str, x: torch.Tensor, conv: nn.Conv2d, train: bool) -> torch.Tensor:
+        """Plain convolution with bias on the generic implicit-GEMM kernel (the 2x2 / stride-2 downsample of ConvNeXt);
+        x: [N,H,W,Cin].  Saved in conv_bn's format, so conv_backward() serves it; the bias gradient is conv_bias_backward's."""
+        co, ci, R, S = conv.weight.shape
+        st, pad = conv.stride[0], conv.padding[0]
+        N, H, W, _ = x.shape
+        P, Q = (H + 2 * pad - R) // st + 1, (W + 2 * pad - S) // st + 1
+        geom = dict(N=N, H=H, W=W, Cin=ci, ldx=ci, P=P, Q=Q, Cout=co, ldy=co, R=R, S=S, stride=st, pad=pad)
+        y = self.ws.get(key + ".y", (N, P, Q, co), self.T)
+        hip.conv_gemm(self.d, 0, x, self.w_fwd(conv.weight), y, bias=self.arena.param_flat(conv.bias), **geom)
+        if train:
+            self.saved[key] = dict(x=x, conv=conv, geom=geom, stem_packed=False, col_input=False)
+        return y
+
+    def conv_bias_backward(self, key: str, g: torch.Tensor, slot: Optional[str]):
+        """g: [N,P,Q,Cout].  Weight gradient (side stream) and data gradient through conv_backward; the bias gradient is the
+        column sum of g, next to the weight gradient."""
+        conv, geom = self.saved[key]["conv"], self.saved[key]["geom"]
+        rows, co = geom["N"] * geom["P"] * geom["Q"], geom["Cout"]
+        self.on_side(lambda: self.colsum2d(g, self.arena.grad_flat(conv.bias), rows, co, co))
+        return self.conv_backward(key, g, slot)

@@ -195,6 +195,65 @@ class _UnicomViT(nn.Module):
         return self.feature(x.reshape(x.shape[0], -1))
 
 
+class _CNLayerNorm2d(nn.LayerNorm):
+    """LayerNorm over the channels of an NCHW tensor (ConvNeXt stem / downsample)."""
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        y = torch.nn.functional.layer_norm(x.permute(0, 2, 3, 1), self.normalized_shape, self.weight, self.bias, self.eps)
+        return y.permute(0, 3, 1, 2)
+
+
+class _CNBlock(nn.Module):
+    def __init__(self, dim: int):
+        super().__init__()
+        self.conv_dw = nn.Conv2d(dim, dim, 7, padding=3, groups=dim)
+        self.norm = nn.LayerNorm(dim, eps=1e-6)
+        self.mlp = _Mlp(dim, 4 * dim)
+        self.gamma = nn.Parameter(torch.ones(dim))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        y = self.conv_dw(x).permute(0, 2, 3, 1)
+        y = self.mlp(self.norm(y)).permute(0, 3, 1, 2)
+        return x + y * self.gamma.reshape(1, -1, 1, 1)
+
+
+class _CNStage(nn.Module):
+    def __init__(self, in_dim: int, dim: int, depth: int, downsample: bool):
+        super().__init__()
+        if downsample:
+            self.downsample = nn.Sequential(_CNLayerNorm2d(in_dim, eps=1e-6), nn.Conv2d(in_dim, dim, 2, 2))
+        else:
+            self.downsample = nn.Identity()
+        self.blocks = nn.Sequential(*[_CNBlock(dim) for _ in range(depth)])
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.blocks(self.downsample(x))
+
+
+class _CNHead(nn.Module):
+    def __init__(self, dim: int):
+        super().__init__()
+        self.norm = nn.LayerNorm(dim, eps=1e-6)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.norm(x.mean((2, 3)))
+
+
+class _ConvNeXt(nn.Module):
+    """timm ConvNeXt layout, restated from memory, parity unpinned (see nkb_classification/convnext.py); dropout is the
+    identity at inference, so the nn.Dropout children (parameter-free) are left out."""
+
+    def __init__(self, depths: List[int], dims: List[int]):
+        super().__init__()
+        self.num_features = dims[-1]
+        self.stem = nn.Sequential(nn.Conv2d(3, dims[0], 4, 4), _CNLayerNorm2d(dims[0], eps=1e-6))
+        self.stages = nn.Sequential(*[_CNStage(dims[max(i - 1, 0)], dims[i], depths[i], i > 0) for i in range(len(dims))])
+        self.head = _CNHead(dims[-1])
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.head(self.stages(self.stem(x)))
+
+
 class _SingleHead(nn.Module):
     def __init__(self, emb_model: nn.Module, emb: int, n: int):
         super().__init__()
@@ -225,6 +284,8 @@ def _backbone_like(hip_backbone) -> nn.Module:
                           len(hip_backbone.blocks), hip_backbone.heads)
     if getattr(hip_backbone, "family", "") == "vit":
         return _ViT(hip_backbone.img, hip_backbone.patch, hip_backbone.num_features, len(hip_backbone.blocks), hip_backbone.heads)
+    if getattr(hip_backbone, "family", "") == "convnext":
+        return _ConvNeXt(list(hip_backbone.depths), list(hip_backbone.dims))
     layers = [len(getattr(hip_backbone, f"layer{i}")) for i in (1, 2, 3, 4)]
     bottleneck = hasattr(getattr(hip_backbone, "layer1")[0], "conv3")
     return _ResNet(bottleneck, layers)
