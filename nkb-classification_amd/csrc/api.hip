@@ -25,6 +25,16 @@ int nkb_check_launch(const char* what) {
     return 0;
 }
 
+int nkb_cu_count() {
+    static int cus = [] {
+        int dev = 0, n = 0;
+        (void)hipGetDevice(&dev);
+        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+        return n > 0 ? n : 256;
+    }();
+    return cus;
+}
+
 extern "C" const char* nkb_last_error() { return g_err; }
 extern "C" int nkb_version() { return 100; }
 

@@ -11,6 +11,7 @@
 // probability tile is already the B operand of the P*V product when V^T is read with the matching key permutation
 // (k-slot (g, j): j < 4 -> key 16*(2t) + 4g + j, j >= 4 -> key 16*(2t+1) + 4g + j - 4), so P never leaves registers.
 #include "common.h"
+#include "prims.h"
 
 #ifdef NKB_ATTN_STAMPS
 // diagnostic build only (scripts/attn_stamps.py): s_memtime of every wave of the LAST 256 workgroups (steady state: the CUs are no longer in
@@ -38,8 +39,6 @@ namespace {
 constexpr int MAXKB = 16;                    // 16-key blocks per row (T <= 256)
 constexpr int DH = 64;
 
-__device__ __forceinline__ int kswz(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
-
 // cooperative load of one head's K and V rows into two swizzled 128-byte-row LDS images; rows >= T are zero.  All global
 // loads are issued before the first LDS store (one memory latency per workgroup; the rolled load->store loop paid one
 // per 256 chunks: 13 round trips for T = 197).
@@ -61,8 +60,8 @@ __device__ __forceinline__ void load_kv(unsigned char* ks, unsigned char* vs, co
 #pragma unroll
     for (int i = 0; i < IT; ++i) {
         const int c = threadIdx.x + NT * i, row = c >> 3, ch = c & 7;
-        if (row < krows) *(u32x4*)(ks + kswz(row, ch)) = kv[i];
-        if (row < vrows) *(u32x4*)(vs + kswz(row, ch)) = vv[i];
+        if (row < krows) *(u32x4*)(ks + swz128(row, ch)) = kv[i];
+        if (row < vrows) *(u32x4*)(vs + swz128(row, ch)) = vv[i];
     }
 }
 
@@ -72,8 +71,8 @@ __device__ __forceinline__ void load_kv(unsigned char* ks, unsigned char* vs, co
 template <int NKB>
 __device__ __forceinline__ void score_tile(const unsigned char* rows_img, const bf16x8 q0, const bf16x8 q1, f32x4 (&acc)[NKB]) {
     const int lane = threadIdx.x & 63, fr = lane & 15, g = lane >> 4;
-    const unsigned char* p0 = rows_img + kswz(fr, g);          // (16 kb + fr) & 7 == fr & 7: +2048 B per key block
-    const unsigned char* p1 = rows_img + kswz(fr, 4 + g);
+    const unsigned char* p0 = rows_img + swz128(fr, g);        // (16 kb + fr) & 7 == fr & 7: +2048 B per key block
+    const unsigned char* p1 = rows_img + swz128(fr, 4 + g);
 #pragma unroll
     for (int kb = 0; kb < NKB; ++kb) {
         const bf16x8 a0 = *(const bf16x8*)(p0 + 2048 * kb);
@@ -83,14 +82,6 @@ __device__ __forceinline__ void score_tile(const unsigned char* rows_img, const 
     }
 }
 
-// sum over the 16 lanes of a DPP row (lanes with the same lane >> 4): every lane ends up with the total
-__device__ __forceinline__ float attn_row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, true));
-    return v;
-}
 __device__ __forceinline__ float group_sum(float v) { v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64); return v; }
 __device__ __forceinline__ float group_max(float v) { v = fmaxf(v, __shfl_xor(v, 16, 64)); v = fmaxf(v, __shfl_xor(v, 32, 64)); return v; }
 
@@ -203,9 +194,9 @@ __global__ __launch_bounds__(512, WPS) void attn_fwd_kernel(const bf16_t* __rest
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const bf16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) bf16x4*)(Vs + 4096 * t + kswz(vr, 2 * i + (pc >> 1)) + 8 * (pc & 1)));
+                    (__attribute__((address_space(3))) bf16x4*)(Vs + 4096 * t + swz128(vr, 2 * i + (pc >> 1)) + 8 * (pc & 1)));
                 const bf16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) bf16x4*)(Vs + 4096 * t + kswz(vr + 16, 2 * i + (pc >> 1)) + 8 * (pc & 1)));
+                    (__attribute__((address_space(3))) bf16x4*)(Vs + 4096 * t + swz128(vr + 16, 2 * i + (pc >> 1)) + 8 * (pc & 1)));
                 const u32x2 lo = __builtin_bit_cast(u32x2, lo4), hi = __builtin_bit_cast(u32x2, hi4);
                 const u32x4 va = {lo[0], lo[1], hi[0], hi[1]};
                 o[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, va), __builtin_bit_cast(bf16x8, pb), o[i], 0, 0, 0);
@@ -258,8 +249,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_ds_kernel(const bf16_t* __res
         f32x4 s[NKB], dp[NKB];
         {   // both score tiles in one walk over the key blocks; the scheduling barrier keeps the fragment loads of later
             // blocks from being hoisted above the MFMAs (that cost 88-160 spilled VGPRs next to the two accumulator sets)
-            const unsigned char* k0 = Ks + kswz(fr, g), *k1 = Ks + kswz(fr, 4 + g);
-            const unsigned char* v0 = Vs + kswz(fr, g), *v1 = Vs + kswz(fr, 4 + g);
+            const unsigned char* k0 = Ks + swz128(fr, g), *k1 = Ks + swz128(fr, 4 + g);
+            const unsigned char* v0 = Vs + swz128(fr, g), *v1 = Vs + swz128(fr, 4 + g);
 #pragma unroll
             for (int kb = 0; kb < NKB; ++kb) {
                 const bf16x8 ka = *(const bf16x8*)(k0 + 2048 * kb), kc = *(const bf16x8*)(k1 + 2048 * kb);
@@ -309,9 +300,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_ds_kernel(const bf16_t* __res
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const bf16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (__attribute__((address_space(3))) bf16x4*)(Ks + 4096 * t + kswz(vr, 2 * i + (pc >> 1)) + 8 * (pc & 1)));
+                        (__attribute__((address_space(3))) bf16x4*)(Ks + 4096 * t + swz128(vr, 2 * i + (pc >> 1)) + 8 * (pc & 1)));
                     const bf16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (__attribute__((address_space(3))) bf16x4*)(Ks + 4096 * t + kswz(vr + 16, 2 * i + (pc >> 1)) + 8 * (pc & 1)));
+                        (__attribute__((address_space(3))) bf16x4*)(Ks + 4096 * t + swz128(vr + 16, 2 * i + (pc >> 1)) + 8 * (pc & 1)));
                     const u32x2 lo = __builtin_bit_cast(u32x2, lo4), hi = __builtin_bit_cast(u32x2, hi4);
                     const u32x4 ka = {lo[0], lo[1], hi[0], hi[1]};
                     o[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, ka), __builtin_bit_cast(bf16x8, pb), o[i], 0, 0, 0);
@@ -400,10 +391,10 @@ __global__ __launch_bounds__(NKB_ATTN_BWD_THREADS, 1) void attn_bwd_fused_kernel
         for (int i = 0; i < IT; ++i) {
             const int c = threadIdx.x + NT * i, row = c >> 3, ch = c & 7;
             if (row >= ROWS) break;                            // (whole waves: ROWS * 8 is a multiple of 256)
-            *(u32x4*)(Qs + kswz(row, ch)) = rq[i];
-            *(u32x4*)(Ks + kswz(row, ch)) = rk[i];
-            *(u32x4*)(Vs + kswz(row, ch)) = rv[i];
-            *(u32x4*)(Ds + kswz(row, ch)) = rd[i];
+            *(u32x4*)(Qs + swz128(row, ch)) = rq[i];
+            *(u32x4*)(Ks + swz128(row, ch)) = rk[i];
+            *(u32x4*)(Vs + swz128(row, ch)) = rv[i];
+            *(u32x4*)(Ds + swz128(row, ch)) = rd[i];
             float fd[8], fo[8], t = 0.f;                       // rows >= T hold zeros
             unpack8(rd[i], fd);
             unpack8(ro[i], fo);
@@ -420,14 +411,14 @@ __global__ __launch_bounds__(NKB_ATTN_BWD_THREADS, 1) void attn_bwd_fused_kernel
     ATTN_STAMP(1);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, g = lane >> 4;
     const float sl2 = scale * 1.4426950408889634f;
-    const int o0 = kswz(fr, g), o1 = kswz(fr, 4 + g);          // fragment offsets of row fr; +2048 per 16-row block
+    const int o0 = swz128(fr, g), o1 = swz128(fr, 4 + g);      // fragment offsets of row fr; +2048 per 16-row block
     const int vr = 4 * g + (fr >> 2), pc = fr & 3;
     // transposed fragment for dh block i of 32-row step t (rows vr and vr + 16 of the step)
     auto tr_frag = [&](const unsigned char* img, int t, int i) -> bf16x8 {
         const bf16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) bf16x4*)(img + 4096 * t + kswz(vr, 2 * i + (pc >> 1)) + 8 * (pc & 1)));
+            (__attribute__((address_space(3))) bf16x4*)(img + 4096 * t + swz128(vr, 2 * i + (pc >> 1)) + 8 * (pc & 1)));
         const bf16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-            (__attribute__((address_space(3))) bf16x4*)(img + 4096 * t + kswz(vr + 16, 2 * i + (pc >> 1)) + 8 * (pc & 1)));
+            (__attribute__((address_space(3))) bf16x4*)(img + 4096 * t + swz128(vr + 16, 2 * i + (pc >> 1)) + 8 * (pc & 1)));
         const u32x2 lo = __builtin_bit_cast(u32x2, lo4), hi = __builtin_bit_cast(u32x2, hi4);
         const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
         return __builtin_bit_cast(bf16x8, v);
@@ -442,7 +433,7 @@ __global__ __launch_bounds__(NKB_ATTN_BWD_THREADS, 1) void attn_bwd_fused_kernel
                           __uint_as_float(pk[i][1] << 16), __uint_as_float(pk[i][1] & 0xffff0000u)};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
-                const float t = attn_row16_sum(valid ? r[e] : 0.f);
+                const float t = row16_sum(valid ? r[e] : 0.f);
                 if (fr == 0) cs[(which * NW + wave) * 64 + 16 * i + 4 * g + e] += t;
             }
         }

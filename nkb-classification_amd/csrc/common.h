@@ -101,6 +101,8 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
 // ---- host-side error plumbing ----
 void nkb_set_error(const char* fmt, ...);
 int nkb_check_launch(const char* what);
+// compute units of the current device (256 if the query fails); asked once per process, for whichever device was current then
+int nkb_cu_count();
 // dst[i] += sum over s < splits of part[s * slab + i], i < n, in split order (conv_igemm.hip): second stage of the
 // deterministic weight gradients.  assign: dst is overwritten ("=", scratch products) instead of accumulated into ("+=")
 int nkb_launch_wgrad_reduce(const float* part, long long slab, int splits, float* dst, long long n, bool assign, hipStream_t stream);

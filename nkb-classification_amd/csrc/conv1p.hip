@@ -16,6 +16,7 @@
 //     channels) and leaves ONE partial-sum row per workgroup: stats[workgroup][2][Cout].
 // The only instructions besides MFMAs in the k-loop: 2 LDS reads per fragment, 4 filter loads per k-tile, the waits.
 #include "common.h"
+#include "prims.h"
 #include "convp.h"
 #include <type_traits>
 
@@ -32,35 +33,43 @@ struct C1Params {
 
 template <int V> using C1I = std::integral_constant<int, V>;
 
-__device__ __forceinline__ void c1_glds16(const unsigned char* src, unsigned char* dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-template <int N> __device__ __forceinline__ void c1_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // "all but the n youngest vector-memory operations have completed", n known only at run time (uniform): 8 .. 26
 __device__ __forceinline__ void c1_vmcnt_dyn(int n) {
     switch (n) {
-#define C1_CASE(k) case k: c1_vmcnt<k>(); break;
+#define C1_CASE(k) case k: wait_vmcnt<k>(); break;
         C1_CASE(8) C1_CASE(9) C1_CASE(10) C1_CASE(11) C1_CASE(12) C1_CASE(13) C1_CASE(14) C1_CASE(15) C1_CASE(16) C1_CASE(17)
         C1_CASE(18) C1_CASE(19) C1_CASE(20) C1_CASE(21) C1_CASE(22) C1_CASE(23) C1_CASE(24) C1_CASE(25) C1_CASE(26)
 #undef C1_CASE
-        default: c1_vmcnt<0>(); break;
+        default: wait_vmcnt<0>(); break;
     }
 }
-#define C1_BARRIER()                                 \
-    do {                                             \
-        asm volatile("" ::: "memory");               \
-        __builtin_amdgcn_s_barrier();                \
-        asm volatile("" ::: "memory");               \
-    } while (0)
 
-__device__ __forceinline__ float c1_row16_sum(float v) {      // sum over the 16 lanes of a DPP row, every lane gets the total
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, true));
-    return v;
-}
+// ---- stage macros of both kernels' k-tile bodies.  They name the locals of the lambda they expand in: bq (two register sets of a
+// fragment pair), b0 / b1 (LDS addresses of the k-tile's two k-steps), a00 .. a11 (the filter fragments), acc, NP ----
+#define C1_ALOAD(dst, ptr, off) asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(dst) : "v"(ptr), "n"(off))
+#define C1_PAIR(set, PR)                                                                                              \
+    do {                                                                                                              \
+        LDS_READ128(bq[set][0][0], b0, 4096 * (PR)); LDS_READ128(bq[set][0][1], b1, 4096 * (PR));                     \
+        LDS_READ128(bq[set][1][0], b0, 4096 * (PR) + 2048); LDS_READ128(bq[set][1][1], b1, 4096 * (PR) + 2048);       \
+    } while (0)
+#define C1_MM(J, bb)                                                                                                  \
+    do {                                                                                                              \
+        const bf16x8 f0 = __builtin_bit_cast(bf16x8, bb[0]), f1 = __builtin_bit_cast(bf16x8, bb[1]);                  \
+        acc[0][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a00, f0, acc[0][J], 0, 0, 0);                             \
+        acc[1][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a10, f0, acc[1][J], 0, 0, 0);                             \
+        acc[0][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a01, f1, acc[0][J], 0, 0, 0);                             \
+        acc[1][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a11, f1, acc[1][J], 0, 0, 0);                             \
+    } while (0)
+// pair PR: request pair PR + 1 into the other register set, wait for this one alone (its four reads are the older ones), multiply
+#define C1_STAGE(PR)                                                                                                  \
+    if constexpr ((PR) < NP) {                                                                                        \
+        constexpr int cur_ = (PR) & 1;                                                                                \
+        if constexpr ((PR) + 1 < NP) { C1_PAIR(cur_ ^ 1, (PR) + 1); LDS_WAIT_QUAD(4, bq[cur_]); }                     \
+        else LDS_WAIT_QUAD(0, bq[cur_]);                                                                              \
+        C1_MM(2 * (PR), bq[cur_][0]);                                                                                 \
+        C1_MM(2 * (PR) + 1, bq[cur_][1]);                                                                             \
+        __builtin_amdgcn_sched_barrier(0);                                                                            \
+    }
 
 // KT: k-tiles of 64 input channels (Cin / 64); NP: pairs of 16-pixel fragments of the workgroup's tile (tile rows = 32 NP).
 // LDS: the activation tile, k-tile-major: [KT][32 NP rows][128 B], chunk c of row r at c ^ (r & 7).
@@ -91,7 +100,7 @@ __global__ __launch_bounds__(512, 1) void conv1p_kernel(const C1Params p) {
         for (int i = 0; i < XP; ++i) {
             const int q = min(wave + 8 * i, XQ - 1);           // (a surplus piece repeats the last one: same bytes, same place)
             const int m = min(row0 + 8 * q + lrow, p.M - 1);
-            c1_glds16((const unsigned char*)p.x + ((size_t)m * (size_t)(p.ldx * 2) + (size_t)(kt * 128 + lch * 16)), d_ + q * 1024);
+            glds16((const unsigned char*)p.x + ((size_t)m * (size_t)(p.ldx * 2) + (size_t)(kt * 128 + lch * 16)), d_ + q * 1024);
         }
     };
 
@@ -103,7 +112,6 @@ __global__ __launch_bounds__(512, 1) void conv1p_kernel(const C1Params p) {
     const size_t wblk = (size_t)256 * p.ldw, wfr = (size_t)4 * p.ldw;
     const bf16_t* wnxt = NB > 1 ? wcur + wblk : wbase;
     u32x4 aq[4][2][2];
-#define C1_ALOAD(dst, ptr, off) asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(dst) : "v"(ptr), "n"(off))
     auto issue_a = [&](auto KTN_, const bf16_t* base, u32x4 (&a)[4][2][2]) {      // k-tile KTN of the block at `base` into set KTN & 3
         constexpr int ktn = decltype(KTN_)::value;
         const bf16_t* b0 = base;
@@ -139,13 +147,13 @@ __global__ __launch_bounds__(512, 1) void conv1p_kernel(const C1Params p) {
         // younger than this k-tile's filter loads: the two k-tiles requested since (8); in the first block the tile pieces issued behind
         // it; in a later block's first two k-tiles the last epilogue's stores
         if constexpr (first) {
-            if constexpr (kt == 0) c1_vmcnt<(KT - 1) * XP + 8>();
-            else if constexpr (kt == 1) c1_vmcnt<(KT - 2) * XP + 8>();
-            else c1_vmcnt<8>();
-            if constexpr (kt <= 2) C1_BARRIER();               // every wave's pieces of k-tile kt (kt = 2: of all the rest) have landed
+            if constexpr (kt == 0) wait_vmcnt<(KT - 1) * XP + 8>();
+            else if constexpr (kt == 1) wait_vmcnt<(KT - 2) * XP + 8>();
+            else wait_vmcnt<8>();
+            if constexpr (kt <= 2) NKB_BARRIER();              // every wave's pieces of k-tile kt (kt = 2: of all the rest) have landed
         } else {
             if constexpr (kt <= 1) c1_vmcnt_dyn(8 + nstores);
-            else c1_vmcnt<8>();
+            else wait_vmcnt<8>();
         }
         asm volatile("" : "+v"(a[kt & 3][0][0]), "+v"(a[kt & 3][0][1]), "+v"(a[kt & 3][1][0]), "+v"(a[kt & 3][1][1]));
         const bf16x8 a00 = __builtin_bit_cast(bf16x8, a[kt & 3][0][0]), a01 = __builtin_bit_cast(bf16x8, a[kt & 3][0][1]);
@@ -154,40 +162,10 @@ __global__ __launch_bounds__(512, 1) void conv1p_kernel(const C1Params p) {
         asm volatile("" : "+v"(b0), "+v"(b1));                 // (opaque BEFORE the add: hoisted, the KT address pairs are spilled, and a
         b0 += kt * KTS; b1 += kt * KTS;                        // scratch reload waits for every load in flight)
         u32x4 bq[2][2][2];                                     // [register set][fragment of the pair][k-step]
-#define C1_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define C1_PAIR(set, PR)                                                                                              \
-    do {                                                                                                              \
-        C1_DSR(bq[set][0][0], b0, 4096 * (PR)); C1_DSR(bq[set][0][1], b1, 4096 * (PR));                               \
-        C1_DSR(bq[set][1][0], b0, 4096 * (PR) + 2048); C1_DSR(bq[set][1][1], b1, 4096 * (PR) + 2048);                 \
-    } while (0)
-#define C1_LANDED(n, set)                                                                                             \
-    asm volatile("s_waitcnt lgkmcnt(" #n ")" : "+v"(bq[set][0][0]), "+v"(bq[set][0][1]), "+v"(bq[set][1][0]), "+v"(bq[set][1][1]))
-#define C1_MM(J, bb)                                                                                                  \
-    do {                                                                                                              \
-        const bf16x8 f0 = __builtin_bit_cast(bf16x8, bb[0]), f1 = __builtin_bit_cast(bf16x8, bb[1]);                  \
-        acc[0][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a00, f0, acc[0][J], 0, 0, 0);                             \
-        acc[1][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a10, f0, acc[1][J], 0, 0, 0);                             \
-        acc[0][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a01, f1, acc[0][J], 0, 0, 0);                             \
-        acc[1][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a11, f1, acc[1][J], 0, 0, 0);                             \
-    } while (0)
-#define C1_STAGE(PR)                                                                                                  \
-    if constexpr ((PR) < NP) {                                                                                        \
-        constexpr int cur_ = (PR) & 1;                                                                                \
-        if constexpr ((PR) + 1 < NP) { C1_PAIR(cur_ ^ 1, (PR) + 1); C1_LANDED(4, cur_); }                             \
-        else C1_LANDED(0, cur_);                                                                                      \
-        C1_MM(2 * (PR), bq[cur_][0]);                                                                                 \
-        C1_MM(2 * (PR) + 1, bq[cur_][1]);                                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                                                            \
-    }
         C1_PAIR(0, 0);
         __builtin_amdgcn_s_setprio(1);
         C1_STAGE(0) C1_STAGE(1) C1_STAGE(2) C1_STAGE(3) C1_STAGE(4) C1_STAGE(5) C1_STAGE(6)
         __builtin_amdgcn_s_setprio(0);
-#undef C1_STAGE
-#undef C1_MM
-#undef C1_LANDED
-#undef C1_PAIR
-#undef C1_DSR
     };
 
     // epilogue of one channel block: y = rnd(acc), sums of y and y^2 over this workgroup's pixels; returns the number of vector-memory
@@ -218,7 +196,7 @@ __global__ __launch_bounds__(512, 1) void conv1p_kernel(const C1Params p) {
             acc[1][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { ssum[e] = c1_row16_sum(ssum[e]); ssq[e] = c1_row16_sum(ssq[e]); }
+        for (int e = 0; e < 8; ++e) { ssum[e] = row16_sum(ssum[e]); ssq[e] = row16_sum(ssq[e]); }
         if (frow == 0) {
             float* srow = p.stats + (size_t)wg * 2 * p.Cout + cch;
             *(f32x4*)(srow) = (f32x4){ssum[0], ssum[1], ssum[2], ssum[3]};
@@ -246,7 +224,6 @@ __global__ __launch_bounds__(512, 1) void conv1p_kernel(const C1Params p) {
         block(C1I<0>{}, nstores, aq);
         nstores = epilogue(nb);
     }
-#undef C1_ALOAD
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -282,7 +259,7 @@ __global__ __launch_bounds__(512, 1) void conv1s_kernel(const C1Params p) {
         for (int i = 0; i < XP; ++i) {
             const int q = min(wave + 8 * i, XQ - 1);
             const int m = min(row0 + 8 * q + lrow, p.M - 1);
-            c1_glds16(xrow + ((size_t)m * (size_t)(p.ldx * 2) + (size_t)(xk * 128)), d_ + q * 1024);
+            glds16(xrow + ((size_t)m * (size_t)(p.ldx * 2) + (size_t)(xk * 128)), d_ + q * 1024);
         }
         if (++xk == KT) xk = 0;
         if (++xs == 3) xs = 0;
@@ -293,7 +270,6 @@ __global__ __launch_bounds__(512, 1) void conv1s_kernel(const C1Params p) {
     const size_t wfr = (size_t)4 * p.ldw;
     int wk = 0, wb = 0;
     u32x4 aq[4][2][2];
-#define C1_ALOAD(dst, ptr, off) asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(dst) : "v"(ptr), "n"(off))
     auto issue_a = [&](auto SET_, u32x4 (&a)[4][2][2]) {
         constexpr int set = decltype(SET_)::value;
         const bf16_t* b0 = wptr;
@@ -323,8 +299,8 @@ __global__ __launch_bounds__(512, 1) void conv1s_kernel(const C1Params p) {
         constexpr int set = decltype(SET_)::value;
         // this k-tile's pieces and filter fragments: younger are the next k-tile's (XP + 4) and, for two k-tiles after an epilogue, its stores
         if (late > 0) { c1_vmcnt_dyn(XP + 4 + nstores); --late; }
-        else c1_vmcnt<XP + 4>();
-        C1_BARRIER();                                          // every wave's pieces; the stage of two k-tiles ago is read out
+        else wait_vmcnt<XP + 4>();
+        NKB_BARRIER();                                         // every wave's pieces; the stage of two k-tiles ago is read out
         issue_x();
         issue_a(C1I<(set + 2) & 3>{}, a);
         asm volatile("" : "+v"(a[set][0][0]), "+v"(a[set][0][1]), "+v"(a[set][1][0]), "+v"(a[set][1][1]));
@@ -333,40 +309,10 @@ __global__ __launch_bounds__(512, 1) void conv1s_kernel(const C1Params p) {
         unsigned b0 = xb0 + rs * KTS, b1 = xb1 + rs * KTS;
         if (++rs == 3) rs = 0;
         u32x4 bq[2][2][2];
-#define C1_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define C1_PAIR(set_, PR)                                                                                             \
-    do {                                                                                                              \
-        C1_DSR(bq[set_][0][0], b0, 4096 * (PR)); C1_DSR(bq[set_][0][1], b1, 4096 * (PR));                             \
-        C1_DSR(bq[set_][1][0], b0, 4096 * (PR) + 2048); C1_DSR(bq[set_][1][1], b1, 4096 * (PR) + 2048);               \
-    } while (0)
-#define C1_LANDED(n, set_)                                                                                            \
-    asm volatile("s_waitcnt lgkmcnt(" #n ")" : "+v"(bq[set_][0][0]), "+v"(bq[set_][0][1]), "+v"(bq[set_][1][0]), "+v"(bq[set_][1][1]))
-#define C1_MM(J, bb)                                                                                                  \
-    do {                                                                                                              \
-        const bf16x8 f0 = __builtin_bit_cast(bf16x8, bb[0]), f1 = __builtin_bit_cast(bf16x8, bb[1]);                  \
-        acc[0][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a00, f0, acc[0][J], 0, 0, 0);                             \
-        acc[1][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a10, f0, acc[1][J], 0, 0, 0);                             \
-        acc[0][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a01, f1, acc[0][J], 0, 0, 0);                             \
-        acc[1][J] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a11, f1, acc[1][J], 0, 0, 0);                             \
-    } while (0)
-#define C1_STAGE(PR)                                                                                                  \
-    if constexpr ((PR) < NP) {                                                                                        \
-        constexpr int cur_ = (PR) & 1;                                                                                \
-        if constexpr ((PR) + 1 < NP) { C1_PAIR(cur_ ^ 1, (PR) + 1); C1_LANDED(4, cur_); }                             \
-        else C1_LANDED(0, cur_);                                                                                      \
-        C1_MM(2 * (PR), bq[cur_][0]);                                                                                 \
-        C1_MM(2 * (PR) + 1, bq[cur_][1]);                                                                             \
-        __builtin_amdgcn_sched_barrier(0);                                                                            \
-    }
         C1_PAIR(0, 0);
         __builtin_amdgcn_s_setprio(1);
         C1_STAGE(0) C1_STAGE(1) C1_STAGE(2) C1_STAGE(3) C1_STAGE(4) C1_STAGE(5) C1_STAGE(6)
         __builtin_amdgcn_s_setprio(0);
-#undef C1_STAGE
-#undef C1_MM
-#undef C1_LANDED
-#undef C1_PAIR
-#undef C1_DSR
     };
 
     for (int nb = 0; nb < NB; ++nb) {
@@ -399,7 +345,7 @@ __global__ __launch_bounds__(512, 1) void conv1s_kernel(const C1Params p) {
             acc[1][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
         }
 #pragma unroll
-        for (int e = 0; e < 8; ++e) { ssum[e] = c1_row16_sum(ssum[e]); ssq[e] = c1_row16_sum(ssq[e]); }
+        for (int e = 0; e < 8; ++e) { ssum[e] = row16_sum(ssum[e]); ssq[e] = row16_sum(ssq[e]); }
         if (frow == 0) {
             float* srow = p.stats + (size_t)wg * 2 * p.Cout + cch;
             *(f32x4*)(srow) = (f32x4){ssum[0], ssum[1], ssum[2], ssum[3]};
@@ -410,18 +356,7 @@ __global__ __launch_bounds__(512, 1) void conv1s_kernel(const C1Params p) {
         nstores = nf + 4;
         late = 2;
     }
-    c1_vmcnt<0>();                                             // (the two k-tiles requested past the end land before the LDS is released)
-#undef C1_ALOAD
-}
-
-int c1_cus() {
-    static int cus = [] {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-    return cus;
+    wait_vmcnt<0>();                                           // (the two k-tiles requested past the end land before the LDS is released)
 }
 
 struct C1Geom { int kt, np, rows, nwg, lds, stream; };
@@ -476,7 +411,7 @@ extern "C" int nkb_conv1p_tiles(int dtype, long long M, int Cin, int ldx, int Co
     if (Cout % 256 != 0 || ldx % 8 != 0 || ldy % 8 != 0 || M < 2048) return 0;
     if (M * (long long)ldy >= (1ll << 31) || M * (long long)ldx >= (1ll << 31)) return 0;
     C1Geom g;
-    if (!c1_geom(M, Cin, Cout, c1_cus(), g) || !c1_worth(g, Cin, Cout)) return 0;
+    if (!c1_geom(M, Cin, Cout, nkb_cu_count(), g) || !c1_worth(g, Cin, Cout)) return 0;
     return g.nwg;
 }
 
@@ -486,7 +421,7 @@ extern "C" int nkb_conv1p_fwd(int dtype, const void* x, const void* w, void* y, 
     if (!tiles) { nkb_set_error("conv1p: shape not eligible (M=%lld Cin=%d Cout=%d)", M, Cin, Cout); return 1; }
     if (!stats) { nkb_set_error("conv1p: missing operand"); return 1; }
     C1Geom g;
-    c1_geom(M, Cin, Cout, c1_cus(), g);
+    c1_geom(M, Cin, Cout, nkb_cu_count(), g);
     C1Params p;
     p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.y = (bf16_t*)y; p.stats = stats;
     p.M = (int)M; p.Cin = Cin; p.ldx = ldx; p.Cout = Cout; p.ldy = ldy; p.ldw = Cin;
@@ -503,3 +438,8 @@ extern "C" int nkb_conv1p_fwd(int dtype, const void* x, const void* w, void* y, 
 #undef C1_GO
     return nkb_check_launch("conv1p");
 }
+
+#undef C1_STAGE
+#undef C1_MM
+#undef C1_PAIR
+#undef C1_ALOAD

@@ -10,6 +10,7 @@
 // MFMA orientation: D[cout][pixel] = W[cout][k] * X[pixel][k]^T, so each lane ends up holding
 // 4 consecutive output channels of one pixel.
 #include "common.h"
+#include "prims.h"
 #include <type_traits>
 
 // ------------------------------------------------------------------------------------------
@@ -25,8 +26,6 @@
 template <typename T> struct MmaTraits;
 template <> struct MmaTraits<bf16_t> { static constexpr int KSTEPS = 2; };  // 2 x (16x16x32) per 128-byte k-tile
 template <> struct MmaTraits<float> { static constexpr int KSTEPS = 8; };   // 8 x (16x16x4)
-
-__device__ __forceinline__ int lds_swz(int row, int chunk) { return row * 128 + ((chunk ^ (row & 7)) << 4); }
 
 // BNB, the epilogue selector (an int, so that the kernels' mangled names stay what profiles and scripts match on):
 //   EPI_GENERAL       every plain epilogue: bias, residual operand, ReLU / GELU-family activations, statistics, fp32 output, row remap
@@ -222,7 +221,7 @@ __global__ __launch_bounds__(256, ((BNB && TC == 128) || TC == 64) ? 3 : 1) void
         }
         if (++ck == cpk) { ck = 0; if (++s == p.S) { s = 0; ++r; } }
     };
-    const int st_off = lds_swz(srow, cc);               // (srow + 32*i) & 7 == srow & 7: rows 32 apart are 4096 B apart
+    const int st_off = swz128(srow, cc);                // (srow + 32*i) & 7 == srow & 7: rows 32 apart are 4096 B apart
     auto store_tile = [&](int buf) {
         unsigned char* base = smem + buf * STAGE_BYTES + st_off;
 #pragma unroll
@@ -245,8 +244,8 @@ __global__ __launch_bounds__(256, ((BNB && TC == 128) || TC == 64) ? 3 : 1) void
     const int frow = lane & 15, fgrp = lane >> 4;
     const int arow0 = wc * (TC / 2) + frow;
     const int brow0 = TC + wp * (TP / 2) + frow;
-    const int a_off0 = lds_swz(arow0, fgrp), a_off1 = lds_swz(arow0, 4 + fgrp);
-    const int b_off0 = lds_swz(brow0, fgrp), b_off1 = lds_swz(brow0, 4 + fgrp);
+    const int a_off0 = swz128(arow0, fgrp), a_off1 = swz128(arow0, 4 + fgrp);
+    const int b_off0 = swz128(brow0, fgrp), b_off1 = swz128(brow0, 4 + fgrp);
 
     // halo: which of this lane's MP pixels have a left / right neighbour in the same image row (bit j)
     unsigned lnb = 0u, rnb = 0u;
@@ -314,9 +313,9 @@ __global__ __launch_bounds__(256, ((BNB && TC == 128) || TC == 64) ? 3 : 1) void
             } else {
                 float a[MC], b[MP];
 #pragma unroll
-                for (int i = 0; i < MC; ++i) a[i] = *(const float*)(base + lds_swz(arow0 + 16 * i, ks) + fgrp * 4);
+                for (int i = 0; i < MC; ++i) a[i] = *(const float*)(base + swz128(arow0 + 16 * i, ks) + fgrp * 4);
 #pragma unroll
-                for (int j = 0; j < MP; ++j) b[j] = *(const float*)(base + lds_swz(brow0 + 16 * j, ks) + fgrp * 4);
+                for (int j = 0; j < MP; ++j) b[j] = *(const float*)(base + swz128(brow0 + 16 * j, ks) + fgrp * 4);
 #pragma unroll
                 for (int i = 0; i < MC; ++i)
 #pragma unroll
@@ -876,10 +875,6 @@ struct WgradParams {   // (every field has a default: a caller writes what its l
     float* bpart = nullptr;
 };
 
-__device__ __forceinline__ int lds_swz256(int row, int ch) {
-    return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
-
 template <typename T>
 __global__ __launch_bounds__(256, 3) void conv_wgrad_kernel(const WgradParams p) {
     constexpr int EPC = DT<T>::EPC;
@@ -978,8 +973,8 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_kernel(const WgradParams p)
         unsigned char* base = smem + buf * STAGE_BYTES;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            *(u32x4*)(base + lds_swz256(srow + 16 * i, cc)) = sa[i];
-            *(u32x4*)(base + TILE_BYTES + lds_swz256(srow + 16 * i, cc)) = sb[i];
+            *(u32x4*)(base + swz256(srow + 16 * i, cc)) = sa[i];
+            *(u32x4*)(base + TILE_BYTES + swz256(srow + 16 * i, cc)) = sb[i];
         }
     };
 
@@ -1010,9 +1005,9 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_kernel(const WgradParams p)
                     const int blk = wr * NB + i;  // 16-channel block inside the 128-wide tile
                     const int row = 32 * kk + 8 * g + q4;
                     const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (__attribute__((address_space(3))) bf16x4*)(A + lds_swz256(row, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
+                        (__attribute__((address_space(3))) bf16x4*)(A + swz256(row, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
                     const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (__attribute__((address_space(3))) bf16x4*)(A + lds_swz256(row + 4, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
+                        (__attribute__((address_space(3))) bf16x4*)(A + swz256(row + 4, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
                     a[i] = (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                 }
 #pragma unroll
@@ -1020,9 +1015,9 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_kernel(const WgradParams p)
                     const int blk = wn * NB + j;
                     const int row = 32 * kk + 8 * g + q4;
                     const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (__attribute__((address_space(3))) bf16x4*)(B + lds_swz256(row, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
+                        (__attribute__((address_space(3))) bf16x4*)(B + swz256(row, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
                     const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                        (__attribute__((address_space(3))) bf16x4*)(B + lds_swz256(row + 4, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
+                        (__attribute__((address_space(3))) bf16x4*)(B + swz256(row + 4, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
                     b[j] = (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
                 }
 #pragma unroll
@@ -1039,12 +1034,12 @@ __global__ __launch_bounds__(256, 3) void conv_wgrad_kernel(const WgradParams p)
 #pragma unroll
                 for (int i = 0; i < NB; ++i) {
                     const int col = (wr * NB + i) * 16 + li;
-                    a[i] = *(const float*)(A + lds_swz256(row, col >> 2) + (col & 3) * 4);
+                    a[i] = *(const float*)(A + swz256(row, col >> 2) + (col & 3) * 4);
                 }
 #pragma unroll
                 for (int j = 0; j < NB; ++j) {
                     const int col = (wn * NB + j) * 16 + li;
-                    b[j] = *(const float*)(B + lds_swz256(row, col >> 2) + (col & 3) * 4);
+                    b[j] = *(const float*)(B + swz256(row, col >> 2) + (col & 3) * 4);
                 }
 #pragma unroll
                 for (int i = 0; i < NB; ++i)

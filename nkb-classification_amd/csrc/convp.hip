@@ -28,6 +28,7 @@
 //   chunk top: X(chunk + 1) x 5 | k-tile g: W(g + 2) x 4 | ... | sub-tile end: NPW stores
 // so "W(g) has landed" is `all but the N youngest done` with N known at compile time (CP_* below).
 #include "common.h"
+#include "prims.h"
 #include "convp.h"
 #include <type_traits>
 
@@ -72,27 +73,6 @@ __device__ unsigned long long convp_stamps[2][8];
 
 typedef int cp_i32x4 __attribute__((ext_vector_type(4)));
 template <int V> using CPI = std::integral_constant<int, V>;
-
-__device__ __forceinline__ void cp_glds16(const unsigned char* src, unsigned char* dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-template <int N> __device__ __forceinline__ void cp_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-#define CP_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
-#define CP_BARRIER()                                 \
-    do {                                             \
-        asm volatile("" ::: "memory");               \
-        __builtin_amdgcn_s_barrier();                \
-        asm volatile("" ::: "memory");               \
-    } while (0)
-
-__device__ __forceinline__ float cp_row16_sum(float v) {      // sum over the 16 lanes of a DPP row, every lane gets the total
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, true));
-    return v;
-}
 
 // Epilogue of one sub-tile, straight from the accumulators: lane (frow, fgrp) holds channels cch .. cch + 7 of pixel m0 + (pw NPW + j) 16 +
 // frow in acc[0][j] | acc[1][j] -> one 16-byte row per fragment.  EPI 0: y = rnd(acc), sums of y and y^2; EPI 1: the fused
@@ -172,7 +152,7 @@ __device__ __forceinline__ void cp_epilogue(const CPParams& p, f32x4 (&acc)[2][N
                 }
                 if (nf > 0) {
     #pragma unroll
-                    for (int e = 0; e < 8; ++e) { ssum[e] = cp_row16_sum(ssum[e]); ssq[e] = cp_row16_sum(ssq[e]); }
+                    for (int e = 0; e < 8; ++e) { ssum[e] = row16_sum(ssum[e]); ssq[e] = row16_sum(ssq[e]); }
                     if (frow == 0) {
     #pragma unroll
                         for (int e = 0; e < 8; ++e) { wsum[e] += ssum[e]; wsum[8 + e] += ssq[e]; }
@@ -223,7 +203,7 @@ __global__ __launch_bounds__(512, 1) void convp_kernel(const CPParams p) {
             const unsigned char* s_ = (const unsigned char*)p.w + (size_t)((wr * 3 + wsx) * cpk + wck) * 128;
             unsigned char* d_ = wslot + (wgi & 1) * 4096;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) cp_glds16(s_ + (size_t)((q & 1) * 16 + (q >> 1) * 4) * wrow + wsrc0, d_ + q * 1024);
+            for (int q = 0; q < 4; ++q) glds16(s_ + (size_t)((q & 1) * 16 + (q >> 1) * 4) * wrow + wsrc0, d_ + q * 1024);
         }
         ++wgi;
         if (++wsx == 3) { wsx = 0; if (++wck == cpk) { wck = 0; if (++wr == 3) wr = 0; } }
@@ -264,7 +244,7 @@ __global__ __launch_bounds__(512, 1) void convp_kernel(const CPParams p) {
                 const bool ok = (xhm >> (3 * i + xr)) & 1u;
                 const unsigned char* s_ = ok ? (const unsigned char*)p.x + (xoff0 + (long)i * 128 * p.ldx + rowoff)
                                              : convp_zero_page + (lane & 7) * 16;
-                cp_glds16(s_, d_ + i * 8192);
+                glds16(s_, d_ + i * 8192);
             }
         }
         ++xg;
@@ -310,11 +290,11 @@ __global__ __launch_bounds__(512, 1) void convp_kernel(const CPParams p) {
     auto overhead = [&](int gk, int s) {
         CP_STAMP(0);
         const bool x_before = ((s + 2) % 3) == xpos;            // the overhead of k-tile gk - 1 issued activation pieces
-        if (gk >= GT - 3) cp_vmcnt<0>();
-        else if (epi_cnt > 0) { if (x_before) cp_vmcnt<9 + NPW>(); else cp_vmcnt<4 + NPW>(); }
-        else { if (x_before) cp_vmcnt<9>(); else cp_vmcnt<4>(); }
+        if (gk >= GT - 3) wait_vmcnt<0>();
+        else if (epi_cnt > 0) { if (x_before) wait_vmcnt<9 + NPW>(); else wait_vmcnt<4 + NPW>(); }
+        else { if (x_before) wait_vmcnt<9>(); else wait_vmcnt<4>(); }
         if (epi_cnt > 0) --epi_cnt;
-        if (!rot && s == 0) CP_BARRIER();                      // every wave's pieces of this chunk have landed; the chunk before is read out
+        if (!rot && s == 0) NKB_BARRIER();                     // every wave's pieces of this chunk have landed; the chunk before is read out
         if (s == xpos) issue_x();                              // next chunk into the stage the previous chunk used
         CP_STAMP(1);
         // filter fragments: inline assembly — a compiler-issued LDS read here makes hipcc wait lgkmcnt(0) in front of every MFMA
@@ -366,7 +346,7 @@ __global__ __launch_bounds__(512, 1) void convp_kernel(const CPParams p) {
 #pragma unroll
                 for (int s = 0; s < 3; ++s, ++g) {
                     if (!rot) overhead(g, s);
-                    else if (s == 0) CP_BARRIER();
+                    else if (s == 0) NKB_BARRIER();
                     // pixel fragments two at a time through two register sets: stage k issues the four LDS reads of pair k + 1 and
                     // then waits for pair k ALONE (lgkmcnt(4)) — as inline assembly, because hipcc's own wait in front of an MFMA
                     // block under a branch is lgkmcnt(0), which parks the wave on the reads it has just issued (36 % of the wave
@@ -397,19 +377,16 @@ __global__ __launch_bounds__(512, 1) void convp_kernel(const CPParams p) {
                             acc[1][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1][1], f1, acc[1][j], 0, 0, 0);
                         }
                     };
-#define CP_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 #define CP_PAIR(set, J)                                                                                               \
     do {                                                                                                              \
-        CP_DSR(bq[set][0][0], ab0, 2048 * (J)); CP_DSR(bq[set][0][1], ab1, 2048 * (J));                               \
-        CP_DSR(bq[set][1][0], ab0, 2048 * ((J) + 1)); CP_DSR(bq[set][1][1], ab1, 2048 * ((J) + 1));                   \
+        LDS_READ128(bq[set][0][0], ab0, 2048 * (J)); LDS_READ128(bq[set][0][1], ab1, 2048 * (J));                     \
+        LDS_READ128(bq[set][1][0], ab0, 2048 * ((J) + 1)); LDS_READ128(bq[set][1][1], ab1, 2048 * ((J) + 1));         \
     } while (0)
-#define CP_LANDED(n, set)                                                                                             \
-    asm volatile("s_waitcnt lgkmcnt(" #n ")" : "+v"(bq[set][0][0]), "+v"(bq[set][0][1]), "+v"(bq[set][1][0]), "+v"(bq[set][1][1]))
 #define CP_STAGE(JG)                                                                                                  \
     if constexpr ((JG) < 2 * NP) {                                                                                    \
         constexpr int cur_ = ((JG) >> 1) & 1;                                                                         \
-        if constexpr ((JG) + 2 < 2 * NP) { CP_PAIR(cur_ ^ 1, (JG) + 2); CP_LANDED(4, cur_); }                         \
-        else CP_LANDED(0, cur_);                                                                                      \
+        if constexpr ((JG) + 2 < 2 * NP) { CP_PAIR(cur_ ^ 1, (JG) + 2); LDS_WAIT_QUAD(4, bq[cur_]); }                 \
+        else LDS_WAIT_QUAD(0, bq[cur_]);                                                                              \
         mm((JG), bq[cur_][0], CPI<0>{});                                                                              \
         mm((JG) + 1, bq[cur_][1], CPI<((JG) + 2 == 2 * NP)>{});                                                       \
         __builtin_amdgcn_sched_barrier(0);                                                                            \
@@ -418,9 +395,7 @@ __global__ __launch_bounds__(512, 1) void convp_kernel(const CPParams p) {
                     if (!CP_DBG(128)) __builtin_amdgcn_s_setprio(1);
                     CP_STAGE(0) CP_STAGE(2) CP_STAGE(4) CP_STAGE(6) CP_STAGE(8) CP_STAGE(10) CP_STAGE(12) CP_STAGE(14)
 #undef CP_STAGE
-#undef CP_LANDED
 #undef CP_PAIR
-#undef CP_DSR
                     __builtin_amdgcn_s_setprio(0);
                     CP_STAMP(4);                               // pixel fragments + MFMAs
                     // rotated group: the next k-tile's overhead, except behind the sub-tile's last k-tile (the epilogue comes first)
@@ -593,7 +568,7 @@ __global__ __launch_bounds__(512, 1) void convp64_kernel(const CPParams p) {
                 const bool ok = (xhm >> (3 * i + xr)) & 1u;
                 const unsigned char* s_ = ok ? (const unsigned char*)p.x + (xoff0 + (long)i * 128 * p.ldx + rowoff)
                                              : convp_zero_page + (lane & 7) * 16;
-                cp_glds16(s_, d_ + i * 8192);
+                glds16(s_, d_ + i * 8192);
             }
         }
         if constexpr (i1 == 5) {
@@ -614,7 +589,7 @@ __global__ __launch_bounds__(512, 1) void convp64_kernel(const CPParams p) {
     for (int kt = 0; kt < 6; ++kt)
 #pragma unroll
         for (int i = 0; i < 2; ++i) asm volatile("" : "+v"(aw[kt][i][0]), "+v"(aw[kt][i][1]));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");           // (nothing else may sit in front of the counted waits)
+    NKB_VMCNT(0);                                              // (nothing else may sit in front of the counted waits)
     issue_x(CPI<0>{}, CPI<0>{}, CPI<5>{});
     issue_x(CPI<1>{}, CPI<0>{}, CPI<5>{});
 
@@ -654,12 +629,12 @@ __global__ __launch_bounds__(512, 1) void convp64_kernel(const CPParams p) {
                 // this wave's pieces of chunk gc have landed: younger than them are only chunk gc + 1's five and, behind an epilogue, its
                 // NPW stores (a full sub-tile: only such a one is followed by another)
                 CP_STAMP(0);
-                if (gc + 1 >= GC) cp_vmcnt<0>();
-                else if (after_epi) cp_vmcnt<5 + NPW>();
-                else cp_vmcnt<5>();
+                if (gc + 1 >= GC) wait_vmcnt<0>();
+                else if (after_epi) wait_vmcnt<5 + NPW>();
+                else wait_vmcnt<5>();
                 after_epi = false;
                 CP_STAMP(1);
-                CP_BARRIER();                                  // every wave's pieces landed; chunk gc - 1 is read out
+                NKB_BARRIER();                                 // every wave's pieces landed; chunk gc - 1 is read out
                 CP_STAMP(2);
                 // chunk gc + 2 goes into the stage of chunk gc - 1: from here on, spread over the pipeline stages below
                 if constexpr (NP == 0) issue_x(CPI<(r + 2) % 3>{}, CPI<0>{}, CPI<5>{});
@@ -680,16 +655,16 @@ __global__ __launch_bounds__(512, 1) void convp64_kernel(const CPParams p) {
                     if constexpr (r == 2) { ab0 += 2 * XS; ab1 += 2 * XS; asm volatile("" : "+v"(ab0), "+v"(ab1)); }
                     const unsigned fa0 = wa0, fa1 = wa1;
                     if constexpr (r == 2 && pr == 0) {
-                        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ar[s & 1][0][0]) : "v"(fa0), "n"((2 * s) * 2048));
-                        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ar[s & 1][0][1]) : "v"(fa1), "n"((2 * s) * 2048));
-                        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ar[s & 1][1][0]) : "v"(fa0), "n"((2 * s + 1) * 2048));
-                        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ar[s & 1][1][1]) : "v"(fa1), "n"((2 * s + 1) * 2048));
+                        LDS_READ128(ar[s & 1][0][0], fa0, (2 * s) * 2048);
+                        LDS_READ128(ar[s & 1][0][1], fa1, (2 * s) * 2048);
+                        LDS_READ128(ar[s & 1][1][0], fa0, (2 * s + 1) * 2048);
+                        LDS_READ128(ar[s & 1][1][1], fa1, (2 * s + 1) * 2048);
                     }
                     if (!CP_DBG(32)) {
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][0][0]) : "v"(ab0), "n"(soff + 2048 * (2 * pr)));
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][0][1]) : "v"(ab1), "n"(soff + 2048 * (2 * pr)));
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][1][0]) : "v"(ab0), "n"(soff + 2048 * (2 * pr + 1)));
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][1][1]) : "v"(ab1), "n"(soff + 2048 * (2 * pr + 1)));
+                    LDS_READ128(bq[set][0][0], ab0, soff + 2048 * (2 * pr));
+                    LDS_READ128(bq[set][0][1], ab1, soff + 2048 * (2 * pr));
+                    LDS_READ128(bq[set][1][0], ab0, soff + 2048 * (2 * pr + 1));
+                    LDS_READ128(bq[set][1][1], ab1, soff + 2048 * (2 * pr + 1));
                     }
                 };
                 auto stage = [&](auto Q_, u32x4 (&bq)[2][2][2], u32x4 (&ar)[2][2][2]) {
@@ -699,11 +674,9 @@ __global__ __launch_bounds__(512, 1) void convp64_kernel(const CPParams p) {
                     if constexpr (more) reads(CPI<(more ? Q + 1 : 0)>{}, bq, ar);
                     if constexpr (NP == 1) issue_x(CPI<(r + 2) % 3>{}, CPI<2 * Q>{}, CPI<(2 * Q + 2 < 5 ? 2 * Q + 2 : 5)>{});
                     else if constexpr (Q < 5) issue_x(CPI<(r + 2) % 3>{}, CPI<(Q < 5 ? Q : 0)>{}, CPI<(Q < 5 ? Q + 1 : 5)>{});
-#define CP_LANDED(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" : "+v"(bq[set][0][0]), "+v"(bq[set][0][1]), "+v"(bq[set][1][0]), "+v"(bq[set][1][1]))
-                    if constexpr (!more) CP_LANDED(0);
-                    else if constexpr (next_a) CP_LANDED(8);
-                    else CP_LANDED(4);
-#undef CP_LANDED
+                    if constexpr (!more) LDS_WAIT_QUAD(0, bq[set]);
+                    else if constexpr (next_a) LDS_WAIT_QUAD(8, bq[set]);
+                    else LDS_WAIT_QUAD(4, bq[set]);
                     if constexpr (r == 2 && pr == 0)
                         asm volatile("" : "+v"(ar[s & 1][0][0]), "+v"(ar[s & 1][0][1]), "+v"(ar[s & 1][1][0]), "+v"(ar[s & 1][1][1]));
                     constexpr int shift = MODE == 0 ? s : 2 - s;
@@ -871,7 +844,7 @@ __global__ __launch_bounds__(512, 1) void convp64h_kernel(const CPParams p) {
 #pragma unroll
             for (int i = i0; i < i1; ++i) {
                 const int m = min(max(xm + 256 * tn + 64 * i, 0), p.M - 1);
-                cp_glds16((const unsigned char*)p.x + ((size_t)m * (size_t)(p.ldx * 2) + (size_t)(lch * 16)), d_ + i * 8192);
+                glds16((const unsigned char*)p.x + ((size_t)m * (size_t)(p.ldx * 2) + (size_t)(lch * 16)), d_ + i * 8192);
             }
         }
     };
@@ -881,7 +854,7 @@ __global__ __launch_bounds__(512, 1) void convp64h_kernel(const CPParams p) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int m = min(row0 + 256 * tn + 8 * wave + lrow + 64 * i, p.M - 1);
-                cp_glds16((const unsigned char*)p.aux + ((size_t)m * (size_t)(p.ldy * 2) + (size_t)(lch * 16)), d_ + i * 8192);
+                glds16((const unsigned char*)p.aux + ((size_t)m * (size_t)(p.ldy * 2) + (size_t)(lch * 16)), d_ + i * 8192);
             }
         }
     };
@@ -895,7 +868,7 @@ __global__ __launch_bounds__(512, 1) void convp64h_kernel(const CPParams p) {
     for (int kt = 0; kt < 6; ++kt)
 #pragma unroll
         for (int i = 0; i < 2; ++i) asm volatile("" : "+v"(aw[kt][i][0]), "+v"(aw[kt][i][1]));
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    NKB_VMCNT(0);
     issue_x(0, CPI<0>{}, CPI<6>{});
 
     for (int t = 0; t < nsub; ++t) {
@@ -929,8 +902,8 @@ __global__ __launch_bounds__(512, 1) void convp64h_kernel(const CPParams p) {
         }
 
         // this wave's pieces of stage t have landed: younger are only the last epilogue's NPW stores (a full sub-tile came before)
-        if (t == 0) cp_vmcnt<0>(); else cp_vmcnt<NPW>();
-        CP_BARRIER();                                          // every wave's pieces; stage t + 1 and the c tile are read out
+        if (t == 0) wait_vmcnt<0>(); else wait_vmcnt<NPW>();
+        NKB_BARRIER();                                         // every wave's pieces; stage t + 1 and the c tile are read out
         if constexpr (EPI == 1) issue_c(t);
         f32x4 acc[2][NPW];
 #pragma unroll
@@ -951,15 +924,15 @@ __global__ __launch_bounds__(512, 1) void convp64h_kernel(const CPParams p) {
                 constexpr int toff = dr * WW * 128;
                 const unsigned ab0 = sa0[dc], ab1 = sa1[dc], fa0 = wa0, fa1 = wa1;
                 if constexpr (r == 2 && pr == 0) {
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ar[s & 1][0][0]) : "v"(fa0), "n"((2 * s) * 2048));
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ar[s & 1][0][1]) : "v"(fa1), "n"((2 * s) * 2048));
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ar[s & 1][1][0]) : "v"(fa0), "n"((2 * s + 1) * 2048));
-                    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(ar[s & 1][1][1]) : "v"(fa1), "n"((2 * s + 1) * 2048));
+                    LDS_READ128(ar[s & 1][0][0], fa0, (2 * s) * 2048);
+                    LDS_READ128(ar[s & 1][0][1], fa1, (2 * s) * 2048);
+                    LDS_READ128(ar[s & 1][1][0], fa0, (2 * s + 1) * 2048);
+                    LDS_READ128(ar[s & 1][1][1], fa1, (2 * s + 1) * 2048);
                 }
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][0][0]) : "v"(ab0), "n"(toff + 2048 * (2 * pr)));
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][0][1]) : "v"(ab1), "n"(toff + 2048 * (2 * pr)));
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][1][0]) : "v"(ab0), "n"(toff + 2048 * (2 * pr + 1)));
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][1][1]) : "v"(ab1), "n"(toff + 2048 * (2 * pr + 1)));
+                LDS_READ128(bq[set][0][0], ab0, toff + 2048 * (2 * pr));
+                LDS_READ128(bq[set][0][1], ab1, toff + 2048 * (2 * pr));
+                LDS_READ128(bq[set][1][0], ab0, toff + 2048 * (2 * pr + 1));
+                LDS_READ128(bq[set][1][1], ab1, toff + 2048 * (2 * pr + 1));
             };
             auto stage = [&](auto Q_, u32x4 (&bq)[2][2][2], u32x4 (&ar)[2][2][2]) {
                 constexpr int Q = decltype(Q_)::value, kt = Q / NPD, pr = Q % NPD, set = Q & 1;
@@ -971,11 +944,9 @@ __global__ __launch_bounds__(512, 1) void convp64h_kernel(const CPParams p) {
                 // DMA pieces of sub-tile t + 1: one in each of the first six stages — early, so that the last one has twelve stages and an
                 // epilogue (~2 us) to land (spread evenly over the 18, the wait at the next sub-tile's top was a third of the wave cycles)
                 if constexpr (Q < 6) issue_x(t + 1, CPI<(Q < 6 ? Q : 0)>{}, CPI<(Q < 6 ? Q + 1 : 1)>{});
-#define CP_LANDED(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" : "+v"(bq[set][0][0]), "+v"(bq[set][0][1]), "+v"(bq[set][1][0]), "+v"(bq[set][1][1]))
-                if constexpr (!more) CP_LANDED(0);
-                else if constexpr (next_a) CP_LANDED(8);
-                else CP_LANDED(4);
-#undef CP_LANDED
+                if constexpr (!more) LDS_WAIT_QUAD(0, bq[set]);
+                else if constexpr (next_a) LDS_WAIT_QUAD(8, bq[set]);
+                else LDS_WAIT_QUAD(4, bq[set]);
                 if constexpr (r == 2 && pr == 0)
                     asm volatile("" : "+v"(ar[s & 1][0][0]), "+v"(ar[s & 1][0][1]), "+v"(ar[s & 1][1][0]), "+v"(ar[s & 1][1][1]));
                 unsigned keepw = dc == 0 ? lnb : rnb, keeph = dr == 0 ? tnb : bnb;
@@ -1035,8 +1006,8 @@ __global__ __launch_bounds__(512, 1) void convp64h_kernel(const CPParams p) {
         const int cch = c_wave + 8 * fgrp;
         if constexpr (EPI == 1) {
             // the c tile: this wave's pieces are older than the (up to) six of stage t + 1; then everybody's
-            if (t + 1 < nsub) cp_vmcnt<6>(); else cp_vmcnt<0>();
-            CP_BARRIER();
+            if (t + 1 < nsub) wait_vmcnt<6>(); else wait_vmcnt<0>();
+            NKB_BARRIER();
         }
         if (!CP_DBG(256)) {
             float sc[8], sh[8], mu[8];
@@ -1080,7 +1051,7 @@ __global__ __launch_bounds__(512, 1) void convp64h_kernel(const CPParams p) {
 
     // ---- partial sums: the 16 pixel lanes of a channel by DPP, the four pixel quarters through LDS
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { ssum[e] = cp_row16_sum(ssum[e]); ssq[e] = cp_row16_sum(ssq[e]); }
+    for (int e = 0; e < 8; ++e) { ssum[e] = row16_sum(ssum[e]); ssq[e] = row16_sum(ssq[e]); }
     float* red = (float*)(smem + ROFF);                        // [PW][2][64]
     if (frow == 0) {
         const int cl = wvc * 32 + 8 * fgrp;
@@ -1101,11 +1072,9 @@ constexpr int CP_LDS = 2 * 40 * 1024 + 8 * 8192 + 2 * 2 * 128 * 4 + 8 * 64 * 4;
 constexpr int CP_LDS64 = 3 * 40 * 1024 + 24 * 1024 + 2048 + 8 * 64 * 4;
 constexpr int CP_LDS64H0 = 2 * 48 * 1024 + 24 * 1024 + 2048 + 1024, CP_LDS64H1 = CP_LDS64H0 + 32 * 1024;
 
-int cp_cus() {
-    static int cus = [] {
-        int dev = 0, n = 0;
-        hipGetDevice(&dev);
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+// once per process, before the first launch (and before its geometry is asked for, as ever): the kernels' dynamic LDS sizes
+void cp_lds_once() {
+    static bool once = [] {
         hipFuncSetAttribute((const void*)convp_kernel<256, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS);
         hipFuncSetAttribute((const void*)convp_kernel<256, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS);
         hipFuncSetAttribute((const void*)convp_kernel<128, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS);
@@ -1114,9 +1083,9 @@ int cp_cus() {
         hipFuncSetAttribute((const void*)convp64_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS64);
         hipFuncSetAttribute((const void*)convp64h_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS64H0);
         hipFuncSetAttribute((const void*)convp64h_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, CP_LDS64H1);
-        return n > 0 ? n : 256;
+        return true;
     }();
-    return cus;
+    (void)once;
 }
 
 struct CPGeom { int tc, tilesN, nwgm, rows_per_wg; };
@@ -1182,8 +1151,9 @@ extern "C" int nkb_convp_tiles(int dtype, int kind, int N, int H, int W, int Cin
     if (M < 4096 || M * (long long)ldx * 2 >= 0xFFFFFF00ll || M * (long long)ldy >= (1ll << 31) ||
         (long long)Cout * 9 * Cin * 2 >= 0xFFFFFF00ll)
         return 0;
+    cp_lds_once();                                             // (every launch asks here first)
     CPGeom g;
-    if (!cp_geom((int)M, Cout, cp_cus() - (kind == 1 ? nkb_rowres_reserved_cus() : 0), g)) return 0;
+    if (!cp_geom((int)M, Cout, nkb_cu_count() - (kind == 1 ? nkb_rowres_reserved_cus() : 0), g)) return 0;
     return g.nwgm;
 }
 
@@ -1201,7 +1171,7 @@ static int convp_launch(int kind, const void* x, const void* w, void* y, const v
     }
     if (!stats || (kind == 1 && (!c || !scale || !shift || !mean))) { nkb_set_error("convp: missing operand"); return 1; }
     CPGeom g;
-    cp_geom(N * H * W, Cout, cp_cus() - (kind == 1 ? nkb_rowres_reserved_cus() : 0), g);
+    cp_geom(N * H * W, Cout, nkb_cu_count() - (kind == 1 ? nkb_rowres_reserved_cus() : 0), g);
     CPParams p;
     p.x = (const bf16_t*)x; p.w = (const bf16_t*)w; p.y = (bf16_t*)y; p.aux = (const bf16_t*)c;
     p.bn_scale = scale; p.bn_shift = shift; p.bn_mean = mean; p.stats = stats;

@@ -25,6 +25,7 @@
 //     for its LDS fragments.
 // All LDS lives in one extern array (a second __shared__ object makes hipcc drain vmcnt before every ds_read).
 #include "common.h"
+#include "prims.h"
 #include "conv_params.h"
 #include "gemm8p.h"
 #include <type_traits>
@@ -90,11 +91,6 @@ struct G8Params {
 #endif
 template <int V> using G8I = std::integral_constant<int, V>;
 
-__device__ __forceinline__ void glds16(const unsigned char* src, unsigned char* dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-
 typedef __attribute__((ext_vector_type(2))) long g8_i64x2;
 template <int F8>
 __device__ __forceinline__ f32x4 g8_mma(const bf16x8& a, const bf16x8& b, f32x4 c) {
@@ -129,15 +125,6 @@ __device__ __forceinline__ f32x4 g8_mma128(const bf16x8& a0, const bf16x8& a1, c
     const g8_i32x8 B = {bl[0], bl[1], bl[2], bl[3], bh[0], bh[1], bh[2], bh[3]};
     // cbsz / blgp: operand formats (0 = e4m3, 1 = e5m2); F8 == 2 multiplies e4m3 weights (A) with e5m2 gradients (B)
     return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(A, B, c, 0, F8 == 2 ? 1 : 0, 0, 0, 0, 0);
-}
-
-// sum over the 16 lanes of a DPP row (quad_perm xor 1, xor 2, row_half_mirror, row_mirror): every lane ends up with the total
-__device__ __forceinline__ float g8_row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, true));
-    return v;
 }
 
 // GELU and its derivative for the epilogue: u = x Phi(x), u' = Phi(x) + x phi(x), Phi through erf by Abramowitz & Stegun 7.1.26
@@ -179,15 +166,6 @@ __device__ __forceinline__ float g8_sload(const float* ptr) {
     asm volatile("s_load_dword %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(ptr) : "memory");
     return __uint_as_float(v);
 }
-// raw s_barrier (no vmcnt drain, unlike __syncthreads) between two compiler-level memory barriers
-#define G8_BARRIER()                                 \
-    do {                                             \
-        asm volatile("" ::: "memory");               \
-        __builtin_amdgcn_s_barrier();                \
-        asm volatile("" ::: "memory");               \
-    } while (0)
-#define G8_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define G8_LGKM(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
 #ifdef NKB_G8_STAMPS
 #define G8_STAMP(slot)                                                                                                \
     do {                                                                                                              \
@@ -370,18 +348,18 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const G8Params p) {
         stream_advance();
         G8_DMA(0, 1, 1); G8_DMA(1, 1, 1); G8_DMA(2, 1, 1);
         stream_advance();
-        G8_VMCNT(6);
+        NKB_VMCNT(6);
     } else {
     G8_ISSUE_AT(0, 0, 0, xo, wo); G8_ISSUE_AT(0, 0, 1, xo, wo); G8_ISSUE_AT(0, 0, 2, xo, wo); G8_ISSUE_AT(0, 0, 3, xo, wo);
     if (GT > 1) {                                  // (DIRECT: KT >= 2, so stream k-tile 1 is k-tile 1 of the first tile)
         G8_ISSUE_AT(1, 1, 0, xo, wo); G8_ISSUE_AT(1, 1, 1, xo, wo); G8_ISSUE_AT(1, 1, 2, xo, wo);
-        G8_VMCNT(6);
+        NKB_VMCNT(6);
     } else {
-        G8_VMCNT(0);
+        NKB_VMCNT(0);
     }
     }
-    G8_BARRIER();
-    if (wr == 1) G8_BARRIER();                    // stagger: the second wave group runs one barrier behind
+    NKB_BARRIER();
+    if (wr == 1) NKB_BARRIER();                   // stagger: the second wave group runs one barrier behind
 
     f32x4 acc[8][4];
 #pragma unroll
@@ -434,7 +412,7 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const G8Params p) {
         const int aux_kind = AUX < 0 ? (p.aux ? 1 + p.aux_mode : (QOUT && p.mask_in ? 3 : 0)) : AUX;   // 0 none, 1 multiply, 2 ReLU6 mask (0 < aux < 6), 3 mask bits
         const int relu = RELU < 0 ? p.relu : RELU;
         const int em0 = tile_m * 256, en0 = tile_n * 256;
-        if constexpr ((NKB_G8_DIAG_EPI & 2) != 0) G8_VMCNT(0);
+        if constexpr ((NKB_G8_DIAG_EPI & 2) != 0) NKB_VMCNT(0);
         float deq = 1.f;
         if constexpr (F8 != 0) deq = g8_sload(p.deq_x) * g8_sload(p.deq_w);
         int lrow = wc * 64 + frow;
@@ -719,15 +697,15 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const G8Params p) {
                     for (int h = 0; h < 2; ++h)
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
-                            const float t_ = g8_row16_sum(cs[h][e]);
+                            const float t_ = row16_sum(cs[h][e]);
                             if (frow == 0) cred[wc * 256 + lcol + 32 * (2 * pp + h) + e] = t_;
                         }
                 }
             }
             if (p.colpart) {                           // (both wave groups are in the epilogue together: align_epi is forced on)
-                G8_BARRIER();
+                NKB_BARRIER();
                 if (tid < 256) p.colpart[(size_t)tile_m * p.N + en0 + tid] = ((cred[tid] + cred[256 + tid]) + cred[512 + tid]) + cred[768 + tid];
-                G8_BARRIER();
+                NKB_BARRIER();
             }
         } else {
 #pragma unroll
@@ -810,53 +788,53 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const G8Params p) {
         }
         G8_ISSUE_AHEAD(1, 3);
         __builtin_amdgcn_sched_barrier(0);
-        G8_LGKM(8);                                // the X reads are retired: their half-tiles may be restaged next phase
-        G8_BARRIER();
-        G8_LGKM(0);
+        NKB_LGKM(8);                               // the X reads are retired: their half-tiles may be restaged next phase
+        NKB_BARRIER();
+        NKB_LGKM(0);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         G8_MMA(0, 0); G8_MMA(1, 1);
         __builtin_amdgcn_s_setprio(0);
-        G8_BARRIER();
+        NKB_BARRIER();
         // ---------------- phase 2: W fragments 4, 5 into the released registers; DMA: X lo of stream k-tile g+2
         a[0][0] = *(const bf16x8*)(pa + fo0 + 2048 * 4); a[0][1] = *(const bf16x8*)(pa + fo1 + 2048 * 4);
         a[1][0] = *(const bf16x8*)(pa + fo0 + 2048 * 5); a[1][1] = *(const bf16x8*)(pa + fo1 + 2048 * 5);
         G8_ISSUE_AHEAD(2, 0);
         __builtin_amdgcn_sched_barrier(0);
-        G8_BARRIER();
-        G8_LGKM(0);
+        NKB_BARRIER();
+        NKB_LGKM(0);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         G8_MMA(2, 2); G8_MMA(3, 3);
         __builtin_amdgcn_s_setprio(0);
-        G8_BARRIER();
+        NKB_BARRIER();
         // ---------------- phase 3: W fragments 6, 7; DMA: X hi of stream k-tile g+2
         a[2][0] = *(const bf16x8*)(pa + fo0 + 2048 * 6); a[2][1] = *(const bf16x8*)(pa + fo1 + 2048 * 6);
         a[3][0] = *(const bf16x8*)(pa + fo0 + 2048 * 7); a[3][1] = *(const bf16x8*)(pa + fo1 + 2048 * 7);
         G8_ISSUE_AHEAD(2, 1);
         __builtin_amdgcn_sched_barrier(0);
-        G8_LGKM(0);                                // last reads of this k-tile's W halves: retired before the barrier, so
-        G8_BARRIER();                              // phase 4 (either wave group) may restage them
+        NKB_LGKM(0);                               // last reads of this k-tile's W halves: retired before the barrier, so
+        NKB_BARRIER();                             // phase 4 (either wave group) may restage them
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         G8_MMA(0, 4); G8_MMA(1, 5);
         __builtin_amdgcn_s_setprio(0);
-        G8_BARRIER();
+        NKB_BARRIER();
         // ---------------- phase 4: no reads; DMA: W lo of stream k-tile g+2; the counted wait that retires k-tile g+1
         G8_ISSUE_AHEAD(2, 2);
         __builtin_amdgcn_sched_barrier(0);
         // (the stream never stops: the three youngest half-tiles are always in flight.  Measured and NOT kept, round 5: W hi of the
         // next k-tile issued in FRONT of the epilogue's stores and this wait counting the stores in (vmcnt(22)) instead of waiting
         // for them — correct, 1 % slower: behind the stores the next half-tiles queue physically, whatever the counter says)
-        if constexpr (SDMA) G8_VMCNT(6);
-        else if (g + 2 < GT) G8_VMCNT(6);
-        else if (g + 1 < GT) G8_VMCNT(0);
-        G8_BARRIER();
+        if constexpr (SDMA) NKB_VMCNT(6);
+        else if (g + 2 < GT) NKB_VMCNT(6);
+        else if (g + 1 < GT) NKB_VMCNT(0);
+        NKB_BARRIER();
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         G8_MMA(2, 6); G8_MMA(3, 7);
         __builtin_amdgcn_s_setprio(0);
-        G8_BARRIER();
+        NKB_BARRIER();
         ++t;
         if constexpr (DIRECT) {
             if (t == KT) {
@@ -865,7 +843,7 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const G8Params p) {
                 // after): run one after the other — each overlapping only 16 MFMAs of the other — the two epilogues cost
                 // 6-10 us per tile, 18-29 % of a K = 768 / 1024 launch; side by side their store latencies overlap.
                 G8_STAMP(4);
-                if (p.align_epi && wr == 0) G8_BARRIER();
+                if (p.align_epi && wr == 0) NKB_BARRIER();
                 G8_STAMP(5);
                 const bool fullt = tile_m * 256 + 256 <= p.M;
                 if constexpr (QOUT) {             // the two producers of the fp8 train step; everything else takes the run-time form
@@ -891,7 +869,7 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const G8Params p) {
                 // once per tile behind the epilogue, tells it that nothing of the epilogue is pending when the loop is re-entered.
                 if constexpr (QOUT) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) only
                 G8_STAMP(6);
-                if (p.align_epi && wr == 1) G8_BARRIER();
+                if (p.align_epi && wr == 1) NKB_BARRIER();
                 G8_STAMP(7);
                 ++tcount;
                 // the next tile becomes the current one; the one after it becomes "next"
@@ -908,8 +886,8 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const G8Params p) {
             }
         }
     }
-    if (wr == 0) G8_BARRIER();
-    if constexpr (SDMA) G8_VMCNT(0);              // the stream's last half-tiles (never read) have landed before the LDS is given back
+    if (wr == 0) NKB_BARRIER();
+    if constexpr (SDMA) NKB_VMCNT(0);             // the stream's last half-tiles (never read) have landed before the LDS is given back
 
     if constexpr (QOUT) {                         // one global atomicMax per workgroup
         __syncthreads();
@@ -1073,7 +1051,7 @@ __global__ __launch_bounds__(512) void gemm8p_ragged_kernel(const G8RParams p) {
             }
     }
     __shared__ unsigned last_flag;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    NKB_VMCNT(0);
     __syncthreads();
     if (threadIdx.x == 0) {
         const unsigned t = __hip_atomic_fetch_add(p.ticket + cb, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1081,7 +1059,7 @@ __global__ __launch_bounds__(512) void gemm8p_ragged_kernel(const G8RParams p) {
         if (last) {
             __hip_atomic_store(p.ticket + cb, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            NKB_VMCNT(0);
         }
         last_flag = last ? 1u : 0u;
     }
@@ -1122,7 +1100,7 @@ __global__ __launch_bounds__(512) void gemm8p_ragged_kernel(const G8RParams p) {
                     // (coherent loads: the pieces were written by other CUs, possibly other dies, and these addresses were read before)
                     if (q0 + q < p.S) asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(t[q][gg]) : "v"(src0 + (size_t)(q0 + q) * pstep + gg * 64) : "memory");
                 }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            NKB_VMCNT(0);
 #pragma unroll
             for (int q = 0; q < QB; ++q)
 #pragma unroll
@@ -1232,9 +1210,9 @@ static unsigned g8_stagger(int tiles, int cus, int kt) {
     return (unsigned)((kt * 3000 + 8000) * 0.85);
 }
 
-static int g8_cus() {
-    static int cus = 0;
-    if (!cus) {
+// once per process, before the first launch: the kernels' dynamic LDS size
+static void g8_lds_once() {
+    static bool once = [] {
         constexpr int lds = 2 * 4 * 128 * 128 + 4096 + 64 + 4096;
         hipFuncSetAttribute((const void*)gemm8p_kernel<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         hipFuncSetAttribute((const void*)gemm8p_kernel<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -1242,12 +1220,9 @@ static int g8_cus() {
         hipFuncSetAttribute((const void*)gemm8p_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         hipFuncSetAttribute((const void*)gemm8p_kernel<true, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         hipFuncSetAttribute((const void*)gemm8p_kernel<true, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-        if (cus <= 0) cus = 256;
-    }
-    return cus;
+        return true;
+    }();
+    (void)once;
 }
 
 // rounds of `tiles` whole tiles on `cus` workgroup slots
@@ -1339,7 +1314,8 @@ int nkb_launch_gemm8p(const ConvParams& cp, hipStream_t stream, const float* row
     const double wbytes = (double)p.N * p.K * 2.0;
     p.group_m = (gm_env > 1 && wbytes > 3.0e6 && p.tilesN >= 6 && p.tilesM >= 2 * gm_env) ? gm_env : 0;
     constexpr int lds = 2 * 4 * 128 * 128 + 4096 + 64 + 4096; // 128 KB (>= the 66.5 KB epilogue tile) + 512 B of bias per wave + the fp8 amax word + 4 KB of column sums
-    const int cus = g8_cus();
+    g8_lds_once();
+    const int cus = nkb_cu_count();
     const int tiles = p.tilesM * p.tilesN;
     // launches with BatchNorm statistics keep the one-tile-per-workgroup form (their partial sums go through LDS)
     constexpr int direct_on = 1;
@@ -1406,7 +1382,8 @@ extern "C" int nkb_gemm_fp8(int mode, const void* xq, const void* wq, void* y, c
     p.tilesM = (M + 255) / 256; p.tilesN = N / 256;
     constexpr int gm_env = NKB_G8_GROUPM;
     p.group_m = (gm_env > 1 && (double)N * K > 3.0e6 && p.tilesN >= 6 && p.tilesM >= 2 * gm_env) ? gm_env : 0;
-    const int cus = g8_cus();
+    g8_lds_once();
+    const int cus = nkb_cu_count();
     constexpr int lds = 2 * 4 * 128 * 128 + 4096 + 64 + 4096;
     const int tiles = p.tilesM * p.tilesN;
     NkbProfScope prof(mode == 0 ? NKB_K_CONV_FWD : NKB_K_CONV_DGRAD, stream, 2.0 * M * (double)N * K);

@@ -15,6 +15,7 @@
 // Everything here is O(Cout * Cin^2) fp32 work on L2-resident operands: tiny next to the launches it replaces, but on the
 // critical path, so each step is one launch with a fixed summation order (bit-reproducible).
 #include "common.h"
+#include "prims.h"
 #include <stdlib.h>
 
 template <typename WT> __device__ __forceinline__ float ldw(const WT* p);
@@ -30,7 +31,6 @@ int nkb_launch_tile_sums(float* stats, int tiles, int C, float* sums, hipStream_
 // weight-gradient kernel's swizzled 256-byte-row image, fragments through ds_read_b64_tr_b16) plus the column sums, and leaves them
 // in its own slab; gram_reduce_kernel adds the slabs in a fixed order.  No second pass over y (a separate Gram launch re-read the
 // 103 MB of layer1's activations at < 1 TB/s: 120 us per block).  C = 64 or 128 (wider stages are small and use nkb_conv_wgrad).
-__device__ __forceinline__ int gswz(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
 
 template <int C>
 __global__ __launch_bounds__(256, 3) void bn_apply_gram_kernel(const bf16_t* __restrict__ c, bf16_t* __restrict__ y,
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256, 3) void bn_apply_gram_kernel(const bf16_t* __r
             u32x4 pk = pack8(v);
             if (r < rows) { if (y) *(u32x4*)(y + (size_t)r * C + cc * 8) = pk; }
             else pk = (u32x4){0u, 0u, 0u, 0u};
-            *(u32x4*)(smem + gswz(srow + RPS * i, cc)) = pk;
+            *(u32x4*)(smem + swz256(srow + RPS * i, cc)) = pk;
             float f[8];
             unpack8(pk, f);                        // the sums see the stored (rounded) values, as the convolution will
 #pragma unroll
@@ -99,18 +99,18 @@ __global__ __launch_bounds__(256, 3) void bn_apply_gram_kernel(const bf16_t* __r
             for (int i = 0; i < NB; ++i) {
                 const int blk = wr * NB + i;
                 const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) bf16x4*)(smem + gswz(row, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
+                    (__attribute__((address_space(3))) bf16x4*)(smem + swz256(row, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
                 const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) bf16x4*)(smem + gswz(row + 4, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
+                    (__attribute__((address_space(3))) bf16x4*)(smem + swz256(row + 4, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
                 a[i] = (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             }
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
                 const int blk = wn * NB + j;
                 const bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) bf16x4*)(smem + gswz(row, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
+                    (__attribute__((address_space(3))) bf16x4*)(smem + swz256(row, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
                 const bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                    (__attribute__((address_space(3))) bf16x4*)(smem + gswz(row + 4, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
+                    (__attribute__((address_space(3))) bf16x4*)(smem + swz256(row + 4, blk * 2 + (p4 >> 1)) + 8 * (p4 & 1)));
                 b[j] = (bf16x8){lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
             }
 #pragma unroll

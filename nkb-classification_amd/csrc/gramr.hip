@@ -13,6 +13,7 @@
 // 1024 / 128 / 256 bytes, their 32-byte channel blocks XOR-swizzled by the pixel on the DMA's source side: conflict-free, brute-forced);
 // every workgroup leaves ONE fp32 slab, summed in workgroup order (nkb_launch_wgrad_reduce) — deterministic, no atomics.
 #include "common.h"
+#include "prims.h"
 #include "convp.h"
 #include <type_traits>
 
@@ -28,23 +29,6 @@ struct GRParams {
 
 __device__ __attribute__((aligned(256))) unsigned char gramr_zero_page[1024];      // zero-initialised: source of rows past the end
 
-__device__ __forceinline__ void gr_glds16(const unsigned char* src, unsigned char* dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-template <int N> __device__ __forceinline__ void gr_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-#define GR_BARRIER()                                 \
-    do {                                             \
-        asm volatile("" ::: "memory");               \
-        __builtin_amdgcn_s_barrier();                \
-        asm volatile("" ::: "memory");               \
-    } while (0)
-
-// 32-byte-block swizzle of pixel row px: rows whose stride is a multiple of 256 bytes all start on bank 0, so the eight rows a 32-lane
-// half reads (pixels 0-3 and 8-11 of a k-step, or 4-7 and 12-15) need eight different block positions: 3 bits from pixel bits 0, 1, 3.
-// 128-byte rows alternate between the two halves of the bank row by themselves: 2 bits from pixel bits 1, 3.
-__device__ __forceinline__ int gr_swz8(int px) { return (px & 3) | (((px >> 3) & 1) << 2); }
-__device__ __forceinline__ int gr_swz4(int px) { return ((px >> 1) & 1) | (((px >> 3) & 1) << 1); }
 
 template <int CO, int CI>
 __global__ __launch_bounds__(512, 1) void gramr_kernel(const GRParams p) {
@@ -76,18 +60,18 @@ __global__ __launch_bounds__(512, 1) void gramr_kernel(const GRParams p) {
             const int e = (wave + 8 * i) * 64 + lane;          // 16-byte element of the stage's g region
             const int px = e / GCH, ch = e % GCH;
             const int m = m0 + px;
-            const unsigned char* src = m < row1 ? (const unsigned char*)p.g + ((size_t)m * (size_t)(p.ldg * 2) + (size_t)((ch ^ (gr_swz8(px) << 1)) << 4))
+            const unsigned char* src = m < row1 ? (const unsigned char*)p.g + ((size_t)m * (size_t)(p.ldg * 2) + (size_t)((ch ^ (swz_px8(px) << 1)) << 4))
                                                 : gramr_zero_page + (lane & 63) * 16;
-            gr_glds16(src, st + (wave + 8 * i) * 1024);
+            glds16(src, st + (wave + 8 * i) * 1024);
         }
         {
             const int e = wave * 64 + lane;
             const int px = e / ACH, ch = e % ACH;
             const int m = m0 + px;
-            const int sw = (AROW == 128 ? gr_swz4(px) : gr_swz8(px)) << 1;
+            const int sw = (AROW == 128 ? swz_px4(px) : swz_px8(px)) << 1;
             const unsigned char* src = m < row1 ? (const unsigned char*)p.a + ((size_t)m * (size_t)(p.lda * 2) + (size_t)((ch ^ sw) << 4))
                                                 : gramr_zero_page + (lane & 63) * 16;
-            gr_glds16(src, st + GST + wave * 1024);
+            glds16(src, st + GST + wave * 1024);
         }
     };
 
@@ -97,8 +81,8 @@ __global__ __launch_bounds__(512, 1) void gramr_kernel(const GRParams p) {
         const int px = 8 * g4 + q4;
 #pragma unroll
         for (int c = 0; c < CF; ++c)
-            aoff[c] = (unsigned)(px * GROW + (((2 * (wave * CF + c) + (p4 >> 1)) ^ (gr_swz8(px) << 1)) << 4) + 8 * (p4 & 1));
-        const int sw = (AROW == 128 ? gr_swz4(px) : gr_swz8(px)) << 1;
+            aoff[c] = (unsigned)(px * GROW + (((2 * (wave * CF + c) + (p4 >> 1)) ^ (swz_px8(px) << 1)) << 4) + 8 * (p4 & 1));
+        const int sw = (AROW == 128 ? swz_px4(px) : swz_px8(px)) << 1;
 #pragma unroll
         for (int j = 0; j < NFR; ++j) boff[j] = (unsigned)(GST + px * AROW + (((2 * j + (p4 >> 1)) ^ sw) << 4) + 8 * (p4 & 1));
     }
@@ -113,12 +97,11 @@ __global__ __launch_bounds__(512, 1) void gramr_kernel(const GRParams p) {
     if (nsteps > 1) issue(1);
 
     for (int s = 0; s < nsteps; ++s) {
-        if (s + 1 < nsteps) gr_vmcnt<5>(); else gr_vmcnt<0>();    // this wave's pieces of stage s: only the next stage's five are younger
-        GR_BARRIER();                                          // every wave's pieces; stage s - 1 is read out
+        if (s + 1 < nsteps) wait_vmcnt<5>(); else wait_vmcnt<0>();  // this wave's pieces of stage s: only the next stage's five are younger
+        NKB_BARRIER();                                         // every wave's pieces; stage s - 1 is read out
         if (s + 2 < nsteps) issue(s + 2);
         asm volatile("" ::: "memory");
         const unsigned sb = lds0 + (unsigned)((s % 3) * STAGE);
-#define GR_TR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
         // (inline assembly: a compiler-visible LDS read behind an LDS-DMA makes hipcc wait for vmcnt(0) — the stages just requested)
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk) {
@@ -126,8 +109,8 @@ __global__ __launch_bounds__(512, 1) void gramr_kernel(const GRParams p) {
 #pragma unroll
             for (int c = 0; c < CF; ++c) {
                 const unsigned ad = sb + aoff[c];
-                if (kk == 0) { GR_TR(fa[c][0], ad, 0); GR_TR(fa[c][1], ad, 4 * GROW); }
-                else { GR_TR(fa[c][0], ad, 32 * GROW); GR_TR(fa[c][1], ad, 36 * GROW); }
+                if (kk == 0) { LDS_READ_TR16(fa[c][0], ad, 0); LDS_READ_TR16(fa[c][1], ad, 4 * GROW); }
+                else { LDS_READ_TR16(fa[c][0], ad, 32 * GROW); LDS_READ_TR16(fa[c][1], ad, 36 * GROW); }
             }
             if constexpr (2 * CF + 8 > 15) {                    // (lgkmcnt counts to 15: eight channel-block reads land before the next eight go out)
 #pragma unroll
@@ -140,8 +123,8 @@ __global__ __launch_bounds__(512, 1) void gramr_kernel(const GRParams p) {
 #pragma unroll
                 for (int jj = 0; jj < 4; ++jj) {
                     const unsigned ad = sb + boff[j0 + jj];
-                    if (kk == 0) { GR_TR(fb[jj][0], ad, 0); GR_TR(fb[jj][1], ad, 4 * AROW); }
-                    else { GR_TR(fb[jj][0], ad, 32 * AROW); GR_TR(fb[jj][1], ad, 36 * AROW); }
+                    if (kk == 0) { LDS_READ_TR16(fb[jj][0], ad, 0); LDS_READ_TR16(fb[jj][1], ad, 4 * AROW); }
+                    else { LDS_READ_TR16(fb[jj][0], ad, 32 * AROW); LDS_READ_TR16(fb[jj][1], ad, 36 * AROW); }
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fb[0][0]), "+v"(fb[0][1]), "+v"(fb[1][0]), "+v"(fb[1][1]), "+v"(fb[2][0]),
                              "+v"(fb[2][1]), "+v"(fb[3][0]), "+v"(fb[3][1]));
@@ -158,7 +141,6 @@ __global__ __launch_bounds__(512, 1) void gramr_kernel(const GRParams p) {
                 }
             }
         }
-#undef GR_TR
     }
 
     // ---- this workgroup's slab: lane (li, g4) of fragment (c, j) holds R[16 (wave CF + c) + 4 g4 + e][16 j + li]
@@ -172,16 +154,6 @@ __global__ __launch_bounds__(512, 1) void gramr_kernel(const GRParams p) {
                 const int co = 16 * (wave * CF + c) + 4 * g4 + e, ci = 16 * j + li;
                 out[p.transposed ? (size_t)ci * CO + co : (size_t)co * CI + ci] = acc[c][j][e];
             }
-}
-
-int gr_cus() {
-    static int cus = [] {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-    return cus;
 }
 
 struct GRGeom { int pxs, rows, nwg; };
@@ -214,7 +186,7 @@ void gr_launch(const GRParams& p, hipStream_t stream) {
 extern "C" long long nkb_gramr_workspace_floats(int dtype, long long M, int co, int ci) {
     if (!nkb_convp_form_enabled(6) || dtype != NKB_DT_BF16 || M < 16384 || M >= (1ll << 31) / 1024) return 0;
     GRGeom g;
-    if (!gr_geom(M, co, ci, gr_cus() - nkb_rowres_reserved_cus(), g)) return 0;
+    if (!gr_geom(M, co, ci, nkb_cu_count() - nkb_rowres_reserved_cus(), g)) return 0;
     return (long long)g.nwg * co * ci;
 }
 
@@ -226,7 +198,7 @@ extern "C" int nkb_gramr(int dtype, const void* g, int ldg, const void* a, int l
     if (!need) { nkb_set_error("gramr: shape not eligible (M=%lld co=%d ci=%d)", M, co, ci); return 1; }
     if (!workspace || workspace_floats < need || ldg % 8 != 0 || lda % 8 != 0 || ldg < co || lda < ci) { nkb_set_error("gramr: bad operand"); return 1; }
     GRGeom gg;
-    gr_geom(M, co, ci, gr_cus() - nkb_rowres_reserved_cus(), gg);
+    gr_geom(M, co, ci, nkb_cu_count() - nkb_rowres_reserved_cus(), gg);
     GRParams p;
     p.g = (const bf16_t*)g; p.a = (const bf16_t*)a; p.part = workspace; p.M = (int)M; p.ldg = ldg; p.lda = lda;
     p.rows_per_wg = gg.rows; p.nwg = gg.nwg; p.transposed = (mode >> 1) & 1;

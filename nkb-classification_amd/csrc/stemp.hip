@@ -19,6 +19,7 @@
 //     requested right behind the barrier of step s (counted s_waitcnt vmcnt);
 //   * 16-byte stores straight from the accumulators, per-lane partial sums in registers, ONE partial-sum row per workgroup.
 #include "common.h"
+#include "prims.h"
 #include "convp.h"
 #include <type_traits>
 
@@ -38,35 +39,16 @@ struct SPParams {
 template <int V> using SPI = std::integral_constant<int, V>;
 constexpr int SP_RING = 32;                        // ring rows (the zero row is row SP_RING)
 
-__device__ __forceinline__ void sp_glds16(const unsigned char* src, unsigned char* dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-template <int N> __device__ __forceinline__ void sp_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void sp_vmcnt_dyn(int n) {          // n uniform, 0 .. 34
     switch (n) {
-#define SP_CASE(k) case k: sp_vmcnt<k>(); break;
+#define SP_CASE(k) case k: wait_vmcnt<k>(); break;
         SP_CASE(1) SP_CASE(2) SP_CASE(3) SP_CASE(4) SP_CASE(5) SP_CASE(6) SP_CASE(7) SP_CASE(8) SP_CASE(9) SP_CASE(10) SP_CASE(11)
         SP_CASE(12) SP_CASE(13) SP_CASE(14) SP_CASE(15) SP_CASE(16) SP_CASE(17) SP_CASE(18) SP_CASE(19) SP_CASE(20) SP_CASE(21)
         SP_CASE(22) SP_CASE(23) SP_CASE(24) SP_CASE(25) SP_CASE(26) SP_CASE(27) SP_CASE(28) SP_CASE(29) SP_CASE(30) SP_CASE(31)
         SP_CASE(32) SP_CASE(33) SP_CASE(34)
 #undef SP_CASE
-        default: sp_vmcnt<0>(); break;
+        default: wait_vmcnt<0>(); break;
     }
-}
-#define SP_BARRIER()                                 \
-    do {                                             \
-        asm volatile("" ::: "memory");               \
-        __builtin_amdgcn_s_barrier();                \
-        asm volatile("" ::: "memory");               \
-    } while (0)
-
-__device__ __forceinline__ float sp_row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xf, 0xf, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xf, 0xf, true));
-    return v;
 }
 
 // FQ: 16-pixel fragments per output row when Q = 16 FQ exactly (the fragment loop is then unrolled: static register sets, immediate
@@ -104,7 +86,7 @@ __global__ __launch_bounds__(512, 1) void stemp_kernel(const SPParams p) {
 #pragma unroll
         for (int r = 0; r < 7; ++r) asm volatile("" : "+v"(aw[r][0]), "+v"(aw[r][1]));      // (hipcc's wait for them lands here, not in the loop)
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    NKB_VMCNT(0);
     __syncthreads();                                           // the ring is zero
 
     // ---- image rows: row yy of image n -> ring row yy & 31, data at byte 32 (four pixels of left margin: window start 2q - 4 >= -4)
@@ -115,8 +97,8 @@ __global__ __launch_bounds__(512, 1) void stemp_kernel(const SPParams p) {
         const unsigned char* src = img + (size_t)yc * p.Wp * 8 + lane * 16;
         unsigned char* dst = smem + (yy & (SP_RING - 1)) * RS + 32;
         const bool ok = yy >= 0 && yy < p.H;
-        if (ok && lane < lanes_row) sp_glds16(src, dst);
-        if (ok && lane + 64 < lanes_row) sp_glds16(src + 1024, dst + 1024);
+        if (ok && lane < lanes_row) glds16(src, dst);
+        if (ok && lane + 64 < lanes_row) glds16(src + 1024, dst + 1024);
     };
     // (the waits below count per wave; `ok` is uniform, so a wave issues a row's instructions or skips them as a whole)
     auto row_ok = [&](int yy) { return yy >= 0 && yy < p.H; };
@@ -139,8 +121,8 @@ __global__ __launch_bounds__(512, 1) void stemp_kernel(const SPParams p) {
     for (int s = 0; s < nsteps; ++s) {
         // rows of step s: this wave's pieces were issued at the top of step s - 2 (the prologue for s < 2) -> younger than them are the
         // stores of steps s - 2 and s - 1 and the pieces issued at the top of step s - 1
-        if (s == 0) sp_vmcnt<0>(); else sp_vmcnt_dyn(nstores_prev + npieces + nstores);
-        SP_BARRIER();                                          // every wave's rows of step s; step s - 1 is read out
+        if (s == 0) wait_vmcnt<0>(); else sp_vmcnt_dyn(nstores_prev + npieces + nstores);
+        NKB_BARRIER();                                         // every wave's rows of step s; step s - 1 is read out
         const int ynew = 2 * (p0 + 4 * (s + 2)) + 2 + wave;    // step s + 2 needs rows up to 2 (p0 + 4 (s + 2)) + 9: eight new ones
         npieces = 0;
         if (s + 2 < nsteps) { issue_row(ynew); npieces = pieces(ynew); }
@@ -187,13 +169,13 @@ __global__ __launch_bounds__(512, 1) void stemp_kernel(const SPParams p) {
             if constexpr (FQ > 0) {
 #define SP_READS_C(set, F)                                                                                            \
     do {                                                                                                              \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][0]) : "v"(rb[0]), "n"(256 * (F)));               \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][1]) : "v"(rb[1]), "n"(256 * (F)));               \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][2]) : "v"(rb[2]), "n"(256 * (F)));               \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][3]) : "v"(rb[3]), "n"(256 * (F)));               \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][4]) : "v"(rb[4]), "n"(256 * (F)));               \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][5]) : "v"(rb[5]), "n"(256 * (F)));               \
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(bq[set][6]) : "v"(rb[6]), "n"(256 * (F)));               \
+        LDS_READ128(bq[set][0], rb[0], 256 * (F));                                                                    \
+        LDS_READ128(bq[set][1], rb[1], 256 * (F));                                                                    \
+        LDS_READ128(bq[set][2], rb[2], 256 * (F));                                                                    \
+        LDS_READ128(bq[set][3], rb[3], 256 * (F));                                                                    \
+        LDS_READ128(bq[set][4], rb[4], 256 * (F));                                                                    \
+        LDS_READ128(bq[set][5], rb[5], 256 * (F));                                                                    \
+        LDS_READ128(bq[set][6], rb[6], 256 * (F));                                                                    \
     } while (0)
 #define SP_FRAG_C(F)                                                                                                  \
     if constexpr ((F) < FQ) {                                                                                         \
@@ -238,8 +220,8 @@ __global__ __launch_bounds__(512, 1) void stemp_kernel(const SPParams p) {
 
     // ---- partial sums: the 16 pixel lanes of a channel by DPP, the four row waves of a channel half through LDS
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { ssum[e] = sp_row16_sum(ssum[e]); ssq[e] = sp_row16_sum(ssq[e]); }
-    SP_BARRIER();                                              // the ring is read out: its tail becomes the reduction scratch
+    for (int e = 0; e < 8; ++e) { ssum[e] = row16_sum(ssum[e]); ssq[e] = row16_sum(ssq[e]); }
+    NKB_BARRIER();                                             // the ring is read out: its tail becomes the reduction scratch
     float* red = (float*)(smem + (SP_RING + 1) * RS);          // [4][2][64]
     if (frow == 0) {
         const int cl = c_half + 8 * fgrp;
@@ -308,8 +290,8 @@ __global__ __launch_bounds__(512, 1) void stempw_kernel(const SWParams p) {
         if (!row_ok(yy)) return 0;
         const unsigned char* src = img + (size_t)yy * p.Wp * 8 + lane * 16;
         unsigned char* dst = smem + (yy % SW_RING) * RS + 32;
-        if (lane < lanes_row) sp_glds16(src, dst);
-        if (lane + 64 < lanes_row) sp_glds16(src + 1024, dst + 1024);
+        if (lane < lanes_row) glds16(src, dst);
+        if (lane + 64 < lanes_row) glds16(src + 1024, dst + 1024);
         return lanes_row > 64 ? 2 : 1;
     };
     // dY row pr -> buffer pr % 6 (the rows of steps s .. s + 2 are live): piece = 8 pixels x 128 B; lane (pixel l >> 3, position l & 7) fetches 16-byte chunk
@@ -320,7 +302,7 @@ __global__ __launch_bounds__(512, 1) void stempw_kernel(const SWParams p) {
         const int px = 8 * piece + (lane >> 3);
         const int sw = (((px >> 1) & 1) | (((px >> 3) & 1) << 1)) << 1;
         const unsigned char* src = (const unsigned char*)p.dy + (((size_t)n * p.P + pr) * p.Q + px) * (size_t)(p.lddy * 2) + (((lane & 7) ^ sw) << 4);
-        if (px < p.Q) sp_glds16(src, dybuf + (pr % 6) * DYB + piece * 1024);
+        if (px < p.Q) glds16(src, dybuf + (pr % 6) * DYB + piece * 1024);
         return 1;
     };
     // step s = output rows p0 + 2 s, + 1: image rows 2 (p0 + 2 s) - 3 .. + 5 (nine; four new per step), dY rows p0 + 2 s, + 1.
@@ -358,7 +340,7 @@ __global__ __launch_bounds__(512, 1) void stempw_kernel(const SWParams p) {
 
     for (int s = 0; s < nsteps; ++s) {
         sp_vmcnt_dyn(pend);
-        SP_BARRIER();                                          // every wave's rows of step s; step s - 1 is read out
+        NKB_BARRIER();                                         // every wave's rows of step s; step s - 1 is read out
         pend = issue_step(s + 2);
         asm volatile("" ::: "memory");
         const int pr = p0 + 2 * s + kh;
@@ -377,20 +359,19 @@ __global__ __launch_bounds__(512, 1) void stempw_kernel(const SWParams p) {
             // (K, half 1) = channel blocks 2-3 against the same window fragments (4 reads, 8 MFMAs).  A unit issues the next unit's reads
             // and waits for its own alone: at most 12 reads in flight (lgkmcnt counts to 15).
             u32x2 fa[4][2], fb[2][4][2];                       // [channel block][pixels + 0 .. 3 | + 4 .. 7]; [k-step parity][fragment][...]
-#define SW_TR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 #define SW_READS0(K)                                                                                                  \
     do {                                                                                                              \
-        SW_TR(fa[0][0], ab[0], 4096 * (K)); SW_TR(fa[0][1], ab[0], 4096 * (K) + 512);                                 \
-        SW_TR(fa[1][0], ab[1], 4096 * (K)); SW_TR(fa[1][1], ab[1], 4096 * (K) + 512);                                 \
-        SW_TR(fb[(K) & 1][0][0], bb[0], 512 * (K)); SW_TR(fb[(K) & 1][0][1], bb[0], 512 * (K) + 64);                  \
-        SW_TR(fb[(K) & 1][1][0], bb[1], 512 * (K)); SW_TR(fb[(K) & 1][1][1], bb[1], 512 * (K) + 64);                  \
-        SW_TR(fb[(K) & 1][2][0], bb[2], 512 * (K)); SW_TR(fb[(K) & 1][2][1], bb[2], 512 * (K) + 64);                  \
-        SW_TR(fb[(K) & 1][3][0], bb[3], 512 * (K)); SW_TR(fb[(K) & 1][3][1], bb[3], 512 * (K) + 64);                  \
+        LDS_READ_TR16(fa[0][0], ab[0], 4096 * (K)); LDS_READ_TR16(fa[0][1], ab[0], 4096 * (K) + 512);                                 \
+        LDS_READ_TR16(fa[1][0], ab[1], 4096 * (K)); LDS_READ_TR16(fa[1][1], ab[1], 4096 * (K) + 512);                                 \
+        LDS_READ_TR16(fb[(K) & 1][0][0], bb[0], 512 * (K)); LDS_READ_TR16(fb[(K) & 1][0][1], bb[0], 512 * (K) + 64);                  \
+        LDS_READ_TR16(fb[(K) & 1][1][0], bb[1], 512 * (K)); LDS_READ_TR16(fb[(K) & 1][1][1], bb[1], 512 * (K) + 64);                  \
+        LDS_READ_TR16(fb[(K) & 1][2][0], bb[2], 512 * (K)); LDS_READ_TR16(fb[(K) & 1][2][1], bb[2], 512 * (K) + 64);                  \
+        LDS_READ_TR16(fb[(K) & 1][3][0], bb[3], 512 * (K)); LDS_READ_TR16(fb[(K) & 1][3][1], bb[3], 512 * (K) + 64);                  \
     } while (0)
 #define SW_READS1(K)                                                                                                  \
     do {                                                                                                              \
-        SW_TR(fa[2][0], ab[2], 4096 * (K)); SW_TR(fa[2][1], ab[2], 4096 * (K) + 512);                                 \
-        SW_TR(fa[3][0], ab[3], 4096 * (K)); SW_TR(fa[3][1], ab[3], 4096 * (K) + 512);                                 \
+        LDS_READ_TR16(fa[2][0], ab[2], 4096 * (K)); LDS_READ_TR16(fa[2][1], ab[2], 4096 * (K) + 512);                                 \
+        LDS_READ_TR16(fa[3][0], ab[3], 4096 * (K)); LDS_READ_TR16(fa[3][1], ab[3], 4096 * (K) + 512);                                 \
     } while (0)
 #define SW_LANDED0(n, K)                                                                                              \
     asm volatile("s_waitcnt lgkmcnt(" #n ")" : "+v"(fa[0][0]), "+v"(fa[0][1]), "+v"(fa[1][0]), "+v"(fa[1][1]), "+v"(fb[(K) & 1][0][0]), \
@@ -428,11 +409,10 @@ __global__ __launch_bounds__(512, 1) void stempw_kernel(const SWParams p) {
 #undef SW_READS1
 #undef SW_READS0
 #undef SW_STEP
-#undef SW_TR
         }
     }
-    sp_vmcnt<0>();
-    SP_BARRIER();                                              // the ring and the dY rows are read out
+    wait_vmcnt<0>();
+    NKB_BARRIER();                                             // the ring and the dY rows are read out
 
     // ---- the two output-row waves of a fragment group add up through LDS; lane (li, g) of fragment (c, j) holds dW[16 c + 4 g + e][16 f + li]
     float* red = (float*)smem;                                 // [4 groups][4 c][4 j][4 e][64 lanes]
@@ -460,16 +440,6 @@ __global__ __launch_bounds__(512, 1) void stempw_kernel(const SWParams p) {
                 }
             }
     }
-}
-
-int sp_cus() {
-    static int cus = [] {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-    return cus;
 }
 
 struct SPGeom { int Wp, P, Q, fq, rs, bands, band_rows, nwg, lds; };
@@ -503,7 +473,7 @@ bool sp_geom(int N, int H, int W, int cus, SPGeom& g) {
 extern "C" int nkb_stemp_tiles(int dtype, int N, int H, int W, int Cout) {
     if (!nkb_convp_form_enabled(5) || dtype != NKB_DT_BF16 || Cout != 64) return 0;
     SPGeom g;
-    if (!sp_geom(N, H, W, sp_cus(), g)) return 0;
+    if (!sp_geom(N, H, W, nkb_cu_count(), g)) return 0;
     if ((long long)N * g.P * g.Q >= (1ll << 31) / 64) return 0;
     return g.nwg;
 }
@@ -514,7 +484,7 @@ extern "C" int nkb_stemp_conv(int dtype, const void* xp, const void* wp, void* y
     if (!tiles) { nkb_set_error("stemp_conv: shape not eligible (N=%d H=%d W=%d Cout=%d)", N, H, W, Cout); return 1; }
     if (!stats || ldy % 8 != 0) { nkb_set_error("stemp_conv: bad operand"); return 1; }
     SPGeom g;
-    sp_geom(N, H, W, sp_cus(), g);
+    sp_geom(N, H, W, nkb_cu_count(), g);
     SPParams p;
     p.xp = (const bf16_t*)xp; p.wp = (const bf16_t*)wp; p.y = (bf16_t*)y; p.stats = stats;
     p.N = N; p.H = H; p.Wp = g.Wp; p.P = g.P; p.Q = g.Q; p.ldy = ldy; p.ldw = 256;
@@ -543,7 +513,7 @@ extern "C" long long nkb_stemp_wgrad_workspace_floats(int dtype, int N, int H, i
     const int tiles = nkb_stemp_tiles(dtype, N, H, W, Cout);
     if (!tiles) return 0;
     SPGeom g;
-    sp_geom(N, H, W, sp_cus(), g);
+    sp_geom(N, H, W, nkb_cu_count(), g);
     if (sw_lds(g) > 160 * 1024 || (g.Q + 31) / 32 > 8) return 0;
     return (long long)tiles * 64 * 224;
 }
@@ -555,7 +525,7 @@ extern "C" int nkb_stemp_wgrad(int dtype, const void* dy, const void* xp, float*
     if (!need) { nkb_set_error("stemp_wgrad: shape not eligible (N=%d H=%d W=%d Cout=%d)", N, H, W, Cout); return 1; }
     if (!workspace || workspace_floats < need || lddy % 8 != 0) { nkb_set_error("stemp_wgrad: bad operand"); return 1; }
     SPGeom g;
-    sp_geom(N, H, W, sp_cus(), g);
+    sp_geom(N, H, W, nkb_cu_count(), g);
     SWParams p;
     p.dy = (const bf16_t*)dy; p.xp = (const bf16_t*)xp; p.part = workspace;
     p.N = N; p.H = H; p.Wp = g.Wp; p.P = g.P; p.Q = g.Q; p.lddy = lddy;

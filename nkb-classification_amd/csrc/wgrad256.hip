@@ -12,15 +12,12 @@
 // SOURCE address because the LDS-DMA destination is linear (wave base + lane * 16).  MFMA fragments come out of LDS with
 // the transposing read ds_read_b64_tr_b16 (both operands are token-major).
 #include "common.h"
+#include "prims.h"
 #include "wgrad256.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) short bf16x4;
-
-__device__ __forceinline__ int swz256(int row, int ch) {
-    return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3)));
-}
 
 struct W256Params {
     const bf16_t* dy;    // [M][lddy]
@@ -46,14 +43,6 @@ struct W256Params {
 // fragments of cout blocks 0-3; phases 2 / 3 re-fill the dY registers the previous phase's MFMAs released (blocks 4-5, 6-7).
 // Restaging follows gemm8p.hip: X halves (last read in phase 1, retired by the lgkmcnt before that phase's barrier) in
 // phases 2 and 3, dY halves (last read in phase 3, retired before its barrier) in phase 4 and the next phase 1.
-#define W8_BARRIER()                                 \
-    do {                                             \
-        asm volatile("" ::: "memory");               \
-        __builtin_amdgcn_s_barrier();                \
-        asm volatile("" ::: "memory");               \
-    } while (0)
-#define W8_VMCNT(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
-#define W8_LGKM(n) asm volatile("s_waitcnt lgkmcnt(" #n ")" ::: "memory")
 
 __device__ __forceinline__ void wgrad8p_body(const W256Params& p, int tile, int split) {
     constexpr int SUB = 64 * 256;                 // one [64 tokens][128 channels] half-tile
@@ -130,9 +119,9 @@ __device__ __forceinline__ void wgrad8p_body(const W256Params& p, int tile, int 
     if (4 < NH) W8_ISSUE(1, 0);
     if (5 < NH) W8_ISSUE(1, 1);
     if (6 < NH) W8_ISSUE(1, 2);
-    if (NH > 4) W8_VMCNT(6); else W8_VMCNT(0);
-    W8_BARRIER();
-    if (wr == 1) W8_BARRIER();
+    if (NH > 4) NKB_VMCNT(6); else NKB_VMCNT(0);
+    NKB_BARRIER();
+    if (wr == 1) NKB_BARRIER();
 
     bf16x8 a[4][2], b[4][2];
 #define W8_MMA(slot, ii)                                                                                              \
@@ -170,51 +159,51 @@ __device__ __forceinline__ void wgrad8p_body(const W256Params& p, int tile, int 
         }
         if (4 * t + 7 < NH) W8_ISSUE(t + 1, 3);
         __builtin_amdgcn_sched_barrier(0);
-        W8_LGKM(15);                               // 32 reads issued, X first: at most 15 outstanding = every X read retired
-        W8_BARRIER();
-        W8_LGKM(0);
+        NKB_LGKM(15);                              // 32 reads issued, X first: at most 15 outstanding = every X read retired
+        NKB_BARRIER();
+        NKB_LGKM(0);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         W8_MMA(0, 0); W8_MMA(1, 1);
         __builtin_amdgcn_s_setprio(0);
-        W8_BARRIER();
+        NKB_BARRIER();
         // ---------------- phase 2
         a[0][0] = frag(A, kxa, 0, 32 * 4); a[0][1] = frag(A, kxa, 1, 32 * 4);
         a[1][0] = frag(A, kxa, 0, 32 * 5); a[1][1] = frag(A, kxa, 1, 32 * 5);
         if (4 * t + 8 < NH) W8_ISSUE(t + 2, 0);
         __builtin_amdgcn_sched_barrier(0);
-        W8_BARRIER();
-        W8_LGKM(0);
+        NKB_BARRIER();
+        NKB_LGKM(0);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         W8_MMA(2, 2); W8_MMA(3, 3);
         __builtin_amdgcn_s_setprio(0);
-        W8_BARRIER();
+        NKB_BARRIER();
         // ---------------- phase 3
         a[2][0] = frag(A, kxa, 0, 32 * 6); a[2][1] = frag(A, kxa, 1, 32 * 6);
         a[3][0] = frag(A, kxa, 0, 32 * 7); a[3][1] = frag(A, kxa, 1, 32 * 7);
         if (4 * t + 9 < NH) W8_ISSUE(t + 2, 1);
         __builtin_amdgcn_sched_barrier(0);
-        W8_LGKM(0);
-        W8_BARRIER();
+        NKB_LGKM(0);
+        NKB_BARRIER();
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         W8_MMA(0, 4); W8_MMA(1, 5);
         __builtin_amdgcn_s_setprio(0);
-        W8_BARRIER();
+        NKB_BARRIER();
         // ---------------- phase 4
         if (4 * t + 10 < NH) W8_ISSUE(t + 2, 2);
         __builtin_amdgcn_sched_barrier(0);
-        if (t + 2 < KT) W8_VMCNT(6);
-        else if (t + 1 < KT) W8_VMCNT(0);
-        W8_BARRIER();
+        if (t + 2 < KT) NKB_VMCNT(6);
+        else if (t + 1 < KT) NKB_VMCNT(0);
+        NKB_BARRIER();
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         W8_MMA(2, 6); W8_MMA(3, 7);
         __builtin_amdgcn_s_setprio(0);
-        W8_BARRIER();
+        NKB_BARRIER();
     }
-    if (wr == 0) W8_BARRIER();
+    if (wr == 0) NKB_BARRIER();
     __syncthreads();
 
     if (do_bias) {
@@ -347,9 +336,9 @@ __device__ __forceinline__ void wgrad8f_body(const W256Params& p, int tile, int 
     if (4 < NH) WF_ISSUE(1, 0);
     if (5 < NH) WF_ISSUE(1, 1);
     if (6 < NH) WF_ISSUE(1, 2);
-    if (NH > 4) W8_VMCNT(6); else W8_VMCNT(0);
-    W8_BARRIER();
-    if (wr == 1) W8_BARRIER();
+    if (NH > 4) NKB_VMCNT(6); else NKB_VMCNT(0);
+    NKB_BARRIER();
+    if (wr == 1) NKB_BARRIER();
 
     w8_i32x8 a[4], b[4];
     // A = dY (e5m2: cbsz 1), B = X (e4m3: blgp 0); scale operands zero = the unscaled instruction
@@ -371,51 +360,51 @@ __device__ __forceinline__ void wgrad8f_body(const W256Params& p, int tile, int 
         for (int i = 0; i < 4; ++i) a[i] = frag(A, kxa, 16 * i);
         if (4 * t + 7 < NH) WF_ISSUE(t + 1, 3);
         __builtin_amdgcn_sched_barrier(0);
-        W8_LGKM(15);                               // 32 reads issued, X first: at most 15 outstanding = every X read retired
-        W8_BARRIER();
-        W8_LGKM(0);
+        NKB_LGKM(15);                              // 32 reads issued, X first: at most 15 outstanding = every X read retired
+        NKB_BARRIER();
+        NKB_LGKM(0);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         WF_MMA(0, 0); WF_MMA(1, 1);
         __builtin_amdgcn_s_setprio(0);
-        W8_BARRIER();
+        NKB_BARRIER();
         // ---------------- phase 2
         a[0] = frag(A, kxa, 16 * 4);
         a[1] = frag(A, kxa, 16 * 5);
         if (4 * t + 8 < NH) WF_ISSUE(t + 2, 0);
         __builtin_amdgcn_sched_barrier(0);
-        W8_BARRIER();
-        W8_LGKM(0);
+        NKB_BARRIER();
+        NKB_LGKM(0);
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         WF_MMA(2, 2); WF_MMA(3, 3);
         __builtin_amdgcn_s_setprio(0);
-        W8_BARRIER();
+        NKB_BARRIER();
         // ---------------- phase 3
         a[2] = frag(A, kxa, 16 * 6);
         a[3] = frag(A, kxa, 16 * 7);
         if (4 * t + 9 < NH) WF_ISSUE(t + 2, 1);
         __builtin_amdgcn_sched_barrier(0);
-        W8_LGKM(0);
-        W8_BARRIER();
+        NKB_LGKM(0);
+        NKB_BARRIER();
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         WF_MMA(0, 4); WF_MMA(1, 5);
         __builtin_amdgcn_s_setprio(0);
-        W8_BARRIER();
+        NKB_BARRIER();
         // ---------------- phase 4
         if (4 * t + 10 < NH) WF_ISSUE(t + 2, 2);
         __builtin_amdgcn_sched_barrier(0);
-        if (t + 2 < KT) W8_VMCNT(6);
-        else if (t + 1 < KT) W8_VMCNT(0);
-        W8_BARRIER();
+        if (t + 2 < KT) NKB_VMCNT(6);
+        else if (t + 1 < KT) NKB_VMCNT(0);
+        NKB_BARRIER();
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_setprio(1);
         WF_MMA(2, 6); WF_MMA(3, 7);
         __builtin_amdgcn_s_setprio(0);
-        W8_BARRIER();
+        NKB_BARRIER();
     }
-    if (wr == 0) W8_BARRIER();
+    if (wr == 0) NKB_BARRIER();
     __syncthreads();
 
     const float deq = *p.deq_g * *p.deq_x;

@@ -27,6 +27,7 @@
 //   * partial results go to per-split slabs that nkb_launch_wgrad_reduce adds in split order (deterministic), or to dW with
 //     fp32 atomics when no workspace is given.
 #include "common.h"
+#include "prims.h"
 #include "wgrad3x3.h"
 
 namespace {
@@ -45,7 +46,6 @@ struct W3Params {
     FastDiv divH1;        // H + 1
 };
 
-__device__ __forceinline__ int swz3(int slot) { return ((slot >> 1) & 1) | (((slot >> 3) & 1) << 1); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // The pipeline (round 4).  The first kernel of this file (rounds 1-3: builtin ds_read_tr16_b64 fragment reads, one k-step of prefetch,
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3p_kernel(const W3Params p) {
         const int sigma = k_begin * 64 + sl;
         const int R = sigma >> PWS, c = sigma & (PW - 1);
         const int n = (int)fdiv((unsigned)R, p.divH1), ri = R - n * H1;
-        const int sc = (((lpos >> 1) ^ swz3(sl)) << 1) | (lpos & 1);
+        const int sc = (((lpos >> 1) ^ swz_px4(sl)) << 1) | (lpos & 1);
         wx[q].ri = ri; wx[q].n = n;
         wx[q].off = (unsigned)((((n * p.H + ri - 1) * p.W + c - 1) * p.ldx + ci0 + sc * 8) * 2);
         xcol[q] = c != 0 && c <= p.W;
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3p_kernel(const W3Params p) {
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int hi = 0; hi < 2; ++hi)
-            va[i][hi] = lds0 + DYOFF + (unsigned)((L0 + 4 * hi) * 128 + 8 * p4 + ((i << 5) ^ (swz3(L0 + 4 * hi) << 5)));
+            va[i][hi] = lds0 + DYOFF + (unsigned)((L0 + 4 * hi) * 128 + 8 * p4 + ((i << 5) ^ (swz_px4(L0 + 4 * hi) << 5)));
     constexpr int NCLS = PWS == 3 ? 6 : 3;
     unsigned tb[NCLS][2];                         // X fragment relative to a 16-slot-aligned ring slot, per low-bits class of the tap
 #pragma unroll
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3p_kernel(const W3Params p) {
 #pragma unroll
         for (int hi = 0; hi < 2; ++hi) {
             const int V = (c >= 3 ? 8 + c - 3 : c) + L0 + 4 * hi;
-            tb[c][hi] = lds0 + (unsigned)(V * 128 + ((wave ^ swz3(V)) << 5) + 8 * p4);
+            tb[c][hi] = lds0 + (unsigned)(V * 128 + ((wave ^ swz_px4(V)) << 5) + 8 * p4);
         }
 
     // With PW = 64 the taps (r = 2, s >= 1) of a k-step's last two dY slots reach two slots into X chunk k + 3 (and, from the last ring
@@ -175,12 +175,10 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3p_kernel(const W3Params p) {
 #pragma unroll
     for (int j = 1; j < D; ++j)
         if (j < nk) { issue_x(); issue_dy(); }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();                  // (not NKB_BARRIER(): the wait's memory clobber is the fence in front)
     asm volatile("" ::: "memory");
 
-#define W3_TR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define W3_WAIT(n, f) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(f[0]), "+v"(f[1]) : "n"(n))
     u32x2 fa[2][4][2], fb[3][2];
     int ub = 0, db = 0;                           // ring slot of X strip slot 64 k (relative to k_begin), byte offset of dY buffer k
     // ring byte offset of the 16-slot-aligned base of tap t of half-step kk, `ahead` k-steps on
@@ -195,12 +193,12 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3p_kernel(const W3Params p) {
 
     // pipeline fill: A fragments of (k-step 0, kk 0), B fragments of units 0 and 1
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { W3_TR(fa[0][i][0], va[i][0], 0); W3_TR(fa[0][i][1], va[i][1], 0); }
+    for (int i = 0; i < 4; ++i) { LDS_READ_TR16(fa[0][i][0], va[i][0], 0); LDS_READ_TR16(fa[0][i][1], va[i][1], 0); }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
         const unsigned sb = xbase(u, 0, 0);
         const unsigned a0 = tb[xcls(u)][0] + sb, a1 = tb[xcls(u)][1] + sb;
-        W3_TR(fb[u][0], a0, 0); W3_TR(fb[u][1], a1, 0);
+        LDS_READ_TR16(fb[u][0], a0, 0); LDS_READ_TR16(fb[u][1], a1, 0);
     }
 
     for (int k = 0; k < nk; ++k) {
@@ -210,9 +208,9 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3p_kernel(const W3Params p) {
             const int kk = u / 9, t = u - 9 * kk;
             if (u == 9) {
                 // ---- the k-step's barrier: k-step k + 1 has landed everywhere, nobody reads k - 1 any more
-                if (k + D - 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (D - 2)) : "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __builtin_amdgcn_s_barrier();
+                if (k + D - 1 < nk) wait_vmcnt<4 * (D - 2)>();
+                else wait_vmcnt<0>();
+                __builtin_amdgcn_s_barrier();      // (not NKB_BARRIER(): the wait's memory clobber is the fence in front)
                 asm volatile("" ::: "memory");
                 if (k + D < nk) { issue_x(); issue_dy(); }
                 asm volatile("" ::: "memory");
@@ -222,19 +220,19 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3p_kernel(const W3Params p) {
                 const int kk2 = uu / 9, t2 = uu - 9 * kk2;
                 const unsigned sb = xbase(t2, kk2, ahead);
                 const unsigned a0 = tb[xcls(t2)][0] + sb, a1 = tb[xcls(t2)][1] + sb;
-                W3_TR(fb[u2 % 3][0], a0, 0); W3_TR(fb[u2 % 3][1], a1, 0);
+                LDS_READ_TR16(fb[u2 % 3][0], a0, 0); LDS_READ_TR16(fb[u2 % 3][1], a1, 0);
             }
             if (t == 5) {                         // A fragments of the next half-step
                 const unsigned boff = (unsigned)(kk == 0 ? db : db_next);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const unsigned a0 = va[i][0] + boff, a1 = va[i][1] + boff;
-                    if (kk == 0) { W3_TR(fa[1][i][0], a0, 4096); W3_TR(fa[1][i][1], a1, 4096); }
-                    else { W3_TR(fa[0][i][0], a0, 0); W3_TR(fa[0][i][1], a1, 0); }
+                    if (kk == 0) { LDS_READ_TR16(fa[1][i][0], a0, 4096); LDS_READ_TR16(fa[1][i][1], a1, 4096); }
+                    else { LDS_READ_TR16(fa[0][i][0], a0, 0); LDS_READ_TR16(fa[0][i][1], a1, 0); }
                 }
             }
             // younger than B(u): B(u+1), B(u+2) — and the eight A reads while they are in between (taps 5, 6, 7)
-            if (t >= 5 && t <= 7) W3_WAIT(12, fb[u % 3]); else W3_WAIT(4, fb[u % 3]);
+            if (t >= 5 && t <= 7) LDS_WAIT_PAIR(12, fb[u % 3]); else LDS_WAIT_PAIR(4, fb[u % 3]);
             const u32x4 vb = {fb[u % 3][0][0], fb[u % 3][0][1], fb[u % 3][1][0], fb[u % 3][1][1]};
             const bf16x8 b_ = __builtin_bit_cast(bf16x8, vb);
 #pragma unroll
@@ -248,8 +246,6 @@ __global__ __launch_bounds__(256, 2) void wgrad3x3p_kernel(const W3Params p) {
         db = db_next;
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // the fragments read past the last k-step (never used)
-#undef W3_TR
-#undef W3_WAIT
 
     // ---- epilogue: acc[i][t][e] = dW[co0 + 16 i + 4 g + e][tap t][ci0 + 16 wave + (lane & 15)]
     const int ci = ci0 + 16 * wave + li;

@@ -20,6 +20,7 @@
 // bias gradient rides on the matrix pipe: one more MFMA per g fragment against an all-ones fragment (the workgroups of a-tile 0).
 // Slabs in split order -> nkb_launch_wgrad_reduce (deterministic), or fp32 atomics without a workspace.
 #include "common.h"
+#include "prims.h"
 #include "wgradr.h"
 #include "convp.h"
 
@@ -38,7 +39,6 @@ struct WRParams {
     int transposed;             // 0: dW[g channel][a channel] (g = dY, a = X); 1: dW[a channel][g channel] (g = X, a = dY)
 };
 
-__device__ __forceinline__ int wr_swz8(int px) { return (px & 3) | (((px >> 3) & 1) << 2); }
 
 template <int D, int WAVES>
 __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void wgradr_kernel(const WRParams p) {
@@ -80,12 +80,12 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void wgradr_kernel(
 #pragma unroll
     for (int i = 0; i < PG; ++i) {
         const int px = gpx + 2 * WAVES * i, ch = lane & 31;
-        og[i] = (unsigned)(((size_t)(row0 + px) * (size_t)p.ldg + g0) * 2 + (size_t)((ch ^ (wr_swz8(px) << 1)) << 4));
+        og[i] = (unsigned)(((size_t)(row0 + px) * (size_t)p.ldg + g0) * 2 + (size_t)((ch ^ (swz_px8(px) << 1)) << 4));
     }
 #pragma unroll
     for (int i = 0; i < PA; ++i) {
         const int px = apx + APP * WAVES * i, ch = lane & (AROW / 16 - 1);
-        oa[i] = (unsigned)(((size_t)(row0 + px) * (size_t)p.lda + a0) * 2 + (size_t)((ch ^ (wr_swz8(px) << 1)) << 4));
+        oa[i] = (unsigned)(((size_t)(row0 + px) * (size_t)p.lda + a0) * 2 + (size_t)((ch ^ (swz_px8(px) << 1)) << 4));
     }
     const unsigned gstep = (unsigned)(32 * p.ldg * 2), astep = (unsigned)(32 * p.lda * 2);
     int remg = nrows - gpx, rema = nrows - apx;       // piece i of the stage is inside the range iff rem > its pixel offset
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void wgradr_kernel(
     // ---- fragment addresses inside a stage (gramr.hip): lane (g4, q4, p4) supplies pixel 8 g4 + q4 (+ 4 through the offset field)
     unsigned va[4], vb[NFR];
     {
-        const int px = 8 * g4 + q4, sw = wr_swz8(px) << 1;
+        const int px = 8 * g4 + q4, sw = swz_px8(px) << 1;
 #pragma unroll
         for (int c = 0; c < 4; ++c) va[c] = lds0 + (unsigned)(px * GROW + (((2 * (4 * wrow + c) + (p4 >> 1)) ^ sw) << 4) + 8 * (p4 & 1));
 #pragma unroll
@@ -134,21 +134,19 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void wgradr_kernel(
 #pragma unroll
     for (int j = 0; j < D; ++j)
         if (j < ns) issue();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
+    wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();                  // (not NKB_BARRIER(): the wait's memory clobber is the fence in front)
     asm volatile("" ::: "memory");
 
-#define WR_TR(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-#define WR_WAIT(n, f) asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(f[0]), "+v"(f[1]) : "n"(n))
     u32x2 fa[2][4][2], fb[4][2];
     unsigned sb = 0;                               // byte offset of the current stage's buffer
     // pipeline fill: the g fragments of stage 0, the a fragments of units 0 and 1.
     // lgkmcnt is a 4-bit counter: a wave keeps at most 15 LDS reads in flight.  The a fragments TWO units ahead: 2 + 4 + the eight g
     // reads = 14 at most; three units ahead (16 around unit 4: the wave stalls on the counter) measured slower — ViT qkv 218 vs 195 us.
 #pragma unroll
-    for (int c = 0; c < 4; ++c) { WR_TR(fa[0][c][0], va[c], 0); WR_TR(fa[0][c][1], va[c], 4 * GROW); }
+    for (int c = 0; c < 4; ++c) { LDS_READ_TR16(fa[0][c][0], va[c], 0); LDS_READ_TR16(fa[0][c][1], va[c], 4 * GROW); }
 #pragma unroll
-    for (int u = 0; u < 2; ++u) { WR_TR(fb[u][0], vb[u], 0); WR_TR(fb[u][1], vb[u], 4 * AROW); }
+    for (int u = 0; u < 2; ++u) { LDS_READ_TR16(fb[u][0], vb[u], 0); LDS_READ_TR16(fb[u][1], vb[u], 4 * AROW); }
 
     // (two stages per iteration: the g fragment sets alternate between two register groups; eight units per stage = two turns of
     // the four a-fragment registers)
@@ -163,12 +161,12 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void wgradr_kernel(
                     if (u == 4) {
                         // ---- the stage's barrier: stage s + 1 has landed everywhere, nobody reads stage s - 1 any more
 #ifdef NKB_WR_SAFE_VM
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        wait_vmcnt<0>();
 #else
-                        if (s + D - 1 < ns) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((PG + PA) * (D - 2)) : "memory");
-                        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        if (s + D - 1 < ns) wait_vmcnt<(PG + PA) * (D - 2)>();
+                        else wait_vmcnt<0>();
 #endif
-                        __builtin_amdgcn_s_barrier();
+                        __builtin_amdgcn_s_barrier();      // (not NKB_BARRIER(): the wait's memory clobber is the fence in front)
                         asm volatile("" ::: "memory");
 #ifndef NKB_WR_NO_DMA
                         if (s + D < ns) issue();
@@ -178,21 +176,21 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void wgradr_kernel(
                     {   // a fragment of unit u + 2 (units 8, 9: the next stage's first two — behind the barrier of unit 4)
                         const int u2 = u + 2;
                         const unsigned ad = vb[u2 % NFR] + (u2 >= NFR ? sb_next : sb);
-                        WR_TR(fb[u2 % 4][0], ad, 0); WR_TR(fb[u2 % 4][1], ad, 4 * AROW);
+                        LDS_READ_TR16(fb[u2 % 4][0], ad, 0); LDS_READ_TR16(fb[u2 % 4][1], ad, 4 * AROW);
                     }
                     if (u == 4) {                  // the g fragments of the next stage
 #pragma unroll
                         for (int c = 0; c < 4; ++c) {
                             const unsigned ad = va[c] + sb_next;
-                            WR_TR(fa[par ^ 1][c][0], ad, 0); WR_TR(fa[par ^ 1][c][1], ad, 4 * GROW);
+                            LDS_READ_TR16(fa[par ^ 1][c][0], ad, 0); LDS_READ_TR16(fa[par ^ 1][c][1], ad, 4 * GROW);
                         }
                     }
                     // younger than this unit's a fragment: the next two — and the eight g reads while they sit in between (units
                     // 4, 5, 6; at unit 7 they are older than its fragment: landed before the next stage needs them)
 #ifdef NKB_WR_SAFE_LGKM
-                    WR_WAIT(0, fb[u % 4]);
+                    LDS_WAIT_PAIR(0, fb[u % 4]);
 #else
-                    if (u >= 4 && u <= 6) WR_WAIT(12, fb[u % 4]); else WR_WAIT(4, fb[u % 4]);
+                    if (u >= 4 && u <= 6) LDS_WAIT_PAIR(12, fb[u % 4]); else LDS_WAIT_PAIR(4, fb[u % 4]);
 #endif
                     const u32x4 vb_ = {fb[u % 4][0][0], fb[u % 4][0][1], fb[u % 4][1][0], fb[u % 4][1][1]};
                     const bf16x8 b_ = __builtin_bit_cast(bf16x8, vb_);
@@ -214,8 +212,6 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void wgradr_kernel(
         }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#undef WR_TR
-#undef WR_WAIT
 
     // ---- this workgroup's tile: lane (li, g4) of fragment (c, j) holds R[g0 + 16 (4 wave + c) + 4 g4 + e][a0 + 16 j + li]
     float* out = p.part ? p.part + (size_t)split * p.slab : p.dw;
@@ -251,16 +247,6 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 2 : 1) void wgradr_kernel(
     }
 }
 
-int wr_cus() {
-    static int cus = [] {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        return n > 0 ? n : 256;
-    }();
-    return cus;
-}
-
 // NKB_WGRAD256: 0 neither this kernel nor wgrad8p, 1 both (default: this one where eligible), 2 wgrad8p only (the round-3 routing)
 int wr_mode() {
     static const int m = [] { const char* e = getenv("NKB_WGRAD256"); return e ? atoi(e) : 1; }();
@@ -269,7 +255,7 @@ int wr_mode() {
 
 struct WRPlan { int tilesG, tilesA, splits, rows, transposed, wide; };
 static void wr_split(long long M, int ntile, WRPlan& g) {
-    const int target = wr_cus() - nkb_rowres_reserved_cus();
+    const int target = nkb_cu_count() - nkb_rowres_reserved_cus();
     int sp = target / ntile;
     if (sp < 1) sp = 1;
     long long rows = (M + sp - 1) / sp;
