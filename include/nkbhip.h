@@ -36,7 +36,7 @@ int nkb_version(void);
 /* Launch counters of the specialised kernels since process start (or the last reset): which = 0 eight-phase GEMM (gemm8p), 1 eight-phase
  * weight gradient (wgrad8p / wgrad256), 2 shared-strip 3x3 weight gradient, 3 fp8 weight gradient, 4 Gram-form closing convolution,
  * 5 bn_apply fused with the Gram matrix, 6 row-balanced 3x3 core (convp), 7 pixel-resident 1x1 expansion (conv1p), 8 ring-buffered stem
- * (stemp: forward and weight gradient), 9 streamed g^T a (gramr), 10 row-streaming 256 x 128-tile 1x1 weight gradient (wgradr), 13 depthwise convolution (dwconv: forward, data and weight gradient), 14 layer scale.  Tests use them to prove that a benchmark configuration took the path it is priced on. */
+ * (stemp: forward and weight gradient), 9 streamed g^T a (gramr), 10 row-streaming 256 x 128-tile 1x1 weight gradient (wgradr), 13 depthwise convolution (dwconv: forward, data and weight gradient), 14 layer scale, 15 narrow 3x3 stem convolution (stem3: forward and data gradient), 16 2x2 average pool (forward and backward).  Tests use them to prove that a benchmark configuration took the path it is priced on. */
 long long nkb_kernel_launches(int which, int reset);
 
 /* Implicit-GEMM convolution / linear layer on MFMA.
@@ -531,6 +531,26 @@ long long nkb_dwconv_wgrad_workspace_floats(int dtype, int N, int H, int W, int 
 int nkb_layer_scale(int dtype, int backward, const void* z, const void* a, const float* gamma, void* out, float* dgamma, long long rows,
                     int C, float* workspace, long long workspace_floats, nkb_stream_t stream);
 long long nkb_layer_scale_workspace_floats(long long rows, int C);
+
+/* Narrow 3x3 / stride 1 / pad 1 convolution on NHWC (csrc/stem3.hip): the second and third convolution of timm's deep stem
+ * (resnet14t / 26t / 26d / 50d), which the reference's default single-task config (configs/singletask_config.py:227, "resnet14t") builds
+ * through timm.create_model at nkb_classification/model.py:82.  Forward (dgrad = 0):
+ *   y[n,h,w,co] = act(bias[co] + sum_{r,s,ci} x[n, h+r-1, w+s-1, ci] * w[co,r,s,ci]),  w = [Cout][3][3][Cin];
+ * data gradient (dgrad = 1): the same sum with x[n, h+1-r, w+1-s, ci] (pass the [Cin][3][3][Cout] data-gradient filter; Cin / ldx then
+ * describe dY, Cout / ldy the produced gradient).  Served (Cin -> Cout): 24->32, 32->32, 32->64, 32->24, 64->32, fp32 (exact-fp32 MFMA)
+ * and bf16; anything else is refused before the launch.  ldx >= Cin, ldy >= Cout (multiples of 16 bytes); padding columns of y are
+ * never written.  bias (optional, fp32 [Cout]) and relu make the eval-mode fold (nkb_wfold) one launch.  stats (optional): one row of
+ * BatchNorm partial sums per workgroup, stats[tiles][2][Cout] = sums of the STORED y and y^2 in a fixed order (no atomics: two launches
+ * give the same bits), for nkb_bn_finalize with tiles = nkb_stem3_tiles(...); buffer of nkb_bn_stats_floats(tiles, Cout) floats.  `tiles`
+ * is checked against the launch when stats is given.  N*H*W*max(ldx, ldy) < 2^31. */
+int nkb_stem3_tiles(int dtype, int N, int H, int W, int Cin, int Cout);
+int nkb_stem3_conv(int dtype, int dgrad, const void* x, const void* w, void* y, const float* bias, float* stats, int N, int H, int W,
+                   int Cin, int ldx, int Cout, int ldy, int R, int relu, int tiles, nkb_stream_t stream);
+/* AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False) of the avg_down projection shortcut (same call site: model.py:82 with
+ * configs/singletask_config.py:227).  forward: in [N][H][W][C] -> out [N][ceil(H/2)][ceil(W/2)][C], an edge window divides by the 1, 2
+ * or 4 pixels inside the map; backward: in = gradient of the pooled map, out[n,h,w,c] = in[n,h/2,w/2,c] / count (every element written).
+ * H, W are the UNPOOLED sizes in both directions.  C % 8 == 0 (bf16) / % 4 (fp32), packed rows; N*H*W*C < 2^31. */
+int nkb_avgpool2x2(int dtype, int backward, const void* in, void* out, int N, int H, int W, int C, nkb_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -39,10 +39,10 @@ extern "C" const char* nkb_last_error() { return g_err; }
 extern "C" int nkb_version() { return 100; }
 
 #include <atomic>
-static std::atomic<long long> g_launches[16];
-void nkb_count_launch(int which) { if ((unsigned)which < 16u) g_launches[which].fetch_add(1, std::memory_order_relaxed); }
+static std::atomic<long long> g_launches[32];
+void nkb_count_launch(int which) { if ((unsigned)which < 32u) g_launches[which].fetch_add(1, std::memory_order_relaxed); }
 extern "C" long long nkb_kernel_launches(int which, int reset) {
-    if ((unsigned)which >= 16u) return -1;
+    if ((unsigned)which >= 32u) return -1;
     return reset ? g_launches[which].exchange(0) : g_launches[which].load();
 }
 
@@ -128,6 +128,6 @@ extern "C" const char* nkb_kernel_name(int kid) {
     static const char* names[] = {"conv_igemm_fwd", "conv_igemm_dgrad", "conv_wgrad", "bn_apply", "bn_bwd_reduce",
                                   "bn_bwd_apply", "bn_finalize", "maxpool", "avgpool", "im2row", "wprep", "loss",
                                   "optim", "misc", "layernorm", "attention", "gelu", "wgrad_reduce", "dwconv_fwd", "dwconv_dgrad",
-                                  "dwconv_wgrad", "layer_scale"};
+                                  "dwconv_wgrad", "layer_scale", "stem3_fwd", "stem3_dgrad", "avgpool2x2"};
     return (kid >= 0 && kid < NKB_K_COUNT) ? names[kid] : "?";
 }

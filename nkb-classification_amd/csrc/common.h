@@ -112,7 +112,7 @@ int nkb_launch_wgrad_reduce2(const float* part, long long slab, int splits, floa
 
 // launch counters of the specialised kernels (api.hip: nkb_kernel_launches) — tests assert from them that the path a benchmark
 // configuration is supposed to take really ran (0 gemm8p, 1 wgrad8p / wgrad256, 2 wgrad3x3, 3 wgrad8f (fp8), 4 Gram-form closing
-// stage (nkb_conv_affine_residual), 5 bn_apply fused with the Gram matrix)
+// stage (nkb_conv_affine_residual), 5 bn_apply fused with the Gram matrix, ..., 15 narrow 3x3 stem convolution (stem3), 16 2x2 average pool)
 void nkb_count_launch(int which);
 
 // per-launch HIP-event profiler (enabled from bench.py); see api.hip
@@ -126,5 +126,5 @@ enum NkbKernelId {
     NKB_K_CONV_FWD = 0, NKB_K_CONV_DGRAD, NKB_K_CONV_WGRAD, NKB_K_BN_APPLY, NKB_K_BN_BWD_REDUCE, NKB_K_BN_BWD_APPLY,
     NKB_K_BN_FINALIZE, NKB_K_MAXPOOL, NKB_K_AVGPOOL, NKB_K_IM2COL, NKB_K_WPREP, NKB_K_LOSS, NKB_K_OPTIM, NKB_K_MISC,
     NKB_K_LN, NKB_K_ATTN, NKB_K_GELU, NKB_K_WGRAD_REDUCE, NKB_K_DWCONV_FWD, NKB_K_DWCONV_DGRAD, NKB_K_DWCONV_WGRAD,
-    NKB_K_LAYER_SCALE, NKB_K_COUNT
+    NKB_K_LAYER_SCALE, NKB_K_STEM3_FWD, NKB_K_STEM3_DGRAD, NKB_K_AVGPOOL2, NKB_K_COUNT
 };

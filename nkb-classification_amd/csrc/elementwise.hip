@@ -703,6 +703,81 @@ extern "C" int nkb_avgpool(int dtype, int backward, const void* in, void* out, i
 }
 
 // ------------------------------------------------------------------------------------------
+// 2x2 / stride-2 average pool with ceil_mode and count_include_pad=False (the avg_down shortcut of timm's ResNet-D/T blocks):
+// [N][H][W][C] -> [N][ceil(H/2)][ceil(W/2)][C]; an edge window divides by the 1, 2 or 4 pixels it really holds.  Backward: every input
+// pixel receives g[h/2][w/2] / count (written, not accumulated).
+template <typename T>
+__global__ void avgpool2x2_fwd_kernel(const T* __restrict__ x, T* __restrict__ y, int N, int H, int W, int C, int P, int Q) {
+    constexpr int NC = Chunk<T>::N;
+    const int cpr = C / NC;
+    const size_t total = (size_t)N * P * Q * cpr;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int cg = (int)(i % cpr);
+        size_t pix = i / cpr;
+        const int q = (int)(pix % Q); pix /= Q;
+        const int pp = (int)(pix % P);
+        const int n = (int)(pix / P);
+        const int nh = min(2, H - 2 * pp), nw = min(2, W - 2 * q);
+        float acc[NC];
+#pragma unroll
+        for (int e = 0; e < NC; ++e) acc[e] = 0.f;
+        for (int r = 0; r < nh; ++r)
+            for (int s = 0; s < nw; ++s) {
+                float v[NC];
+                Chunk<T>::load(x + (((size_t)n * H + 2 * pp + r) * W + 2 * q + s) * C + cg * NC, v);
+#pragma unroll
+                for (int e = 0; e < NC; ++e) acc[e] += v[e];
+            }
+        const float inv = 1.f / (float)(nh * nw);              // 1, 1/2, 1/4: exact
+#pragma unroll
+        for (int e = 0; e < NC; ++e) acc[e] *= inv;
+        Chunk<T>::store(y + i * NC, acc);
+    }
+}
+template <typename T>
+__global__ void avgpool2x2_bwd_kernel(const T* __restrict__ g, T* __restrict__ dx, int N, int H, int W, int C, int P, int Q) {
+    constexpr int NC = Chunk<T>::N;
+    const int cpr = C / NC;
+    const size_t total = (size_t)N * H * W * cpr;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int cg = (int)(i % cpr);
+        size_t pix = i / cpr;
+        const int w = (int)(pix % W); pix /= W;
+        const int h = (int)(pix % H);
+        const int n = (int)(pix / H);
+        const int pp = h >> 1, q = w >> 1;
+        const float inv = 1.f / (float)(min(2, H - 2 * pp) * min(2, W - 2 * q));
+        float v[NC];
+        Chunk<T>::load(g + (((size_t)n * P + pp) * Q + q) * C + cg * NC, v);
+#pragma unroll
+        for (int e = 0; e < NC; ++e) v[e] *= inv;
+        Chunk<T>::store(dx + i * NC, v);
+    }
+}
+extern "C" int nkb_avgpool2x2(int dtype, int backward, const void* in, void* out, int N, int H, int W, int C, hipStream_t stream) {
+    if (dtype != NKB_DT_F32 && dtype != NKB_DT_BF16) { nkb_set_error("avgpool2x2: bad dtype %d", dtype); return 1; }
+    const int n = dtype == NKB_DT_BF16 ? 8 : 4;
+    if (C < n || C % n) { nkb_set_error("avgpool2x2: C=%d not a multiple of %d", C, n); return 1; }
+    if (N < 1 || H < 1 || W < 1 || (double)N * H * W * C >= 2147483648.0) {
+        nkb_set_error("avgpool2x2: operand exceeds 2^31 elements (N=%d H=%d W=%d C=%d)", N, H, W, C);
+        return 1;
+    }
+    const int P = (H + 1) / 2, Q = (W + 1) / 2;
+    const double esz = dtype == NKB_DT_BF16 ? 2.0 : 4.0;
+    NkbProfScope prof(NKB_K_AVGPOOL2, stream, 0, esz * C * ((double)N * H * W + (double)N * P * Q));
+    nkb_count_launch(16);
+    const size_t total = backward ? (size_t)N * H * W * (C / n) : (size_t)N * P * Q * (C / n);
+    if (dtype == NKB_DT_BF16) {
+        if (!backward) hipLaunchKernelGGL(avgpool2x2_fwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, stream, (const bf16_t*)in, (bf16_t*)out, N, H, W, C, P, Q);
+        else hipLaunchKernelGGL(avgpool2x2_bwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, stream, (const bf16_t*)in, (bf16_t*)out, N, H, W, C, P, Q);
+    } else {
+        if (!backward) hipLaunchKernelGGL(avgpool2x2_fwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, stream, (const float*)in, (float*)out, N, H, W, C, P, Q);
+        else hipLaunchKernelGGL(avgpool2x2_bwd_kernel<float>, dim3(grid_for(total)), dim3(256), 0, stream, (const float*)in, (float*)out, N, H, W, C, P, Q);
+    }
+    return nkb_check_launch("avgpool2x2");
+}
+
+// ------------------------------------------------------------------------------------------
 // Stem im2row: NCHW fp32 image -> [N*P*Q][Kp] rows with k = (r*S + s)*Cin + c (zero beyond R*S*Cin),
 // the K order of a channels-last [Cout][R][S][Cin] filter.  Generic in (R,S,stride,pad,Cin): also the
 // ViT patch embedding (k=s=16).

@@ -53,3 +53,6 @@ __device__ __forceinline__ int swz256(int row, int ch) { return 256 * row + 16 *
 // 128-byte rows alternate between the two halves of the bank row by themselves: 2 bits from pixel bits 1, 3.
 __device__ __forceinline__ int swz_px8(int px) { return (px & 3) | (((px >> 3) & 1) << 2); }
 __device__ __forceinline__ int swz_px4(int px) { return ((px >> 1) & 1) | (((px >> 3) & 1) << 1); }
+// linear-address form for windows whose pixel stride is 48 .. 256 bytes (csrc/stem3.hip): 16-byte chunk index ^ address bits 8-10.  The
+// sixteen pixels a quarter wave reads at one k-offset (stride 64 / 128 bytes) land on sixteen different 16-byte bank groups.
+__device__ __forceinline__ int swz_lin(int byte_off) { return byte_off ^ (((byte_off >> 8) & 7) << 4); }

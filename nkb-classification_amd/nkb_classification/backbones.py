@@ -67,13 +67,31 @@ class _Bottle(_ParamOnly):
 
 
 class HipResNet(_ParamOnly):
-    """timm `resnet*` parameter layout: conv1/bn1, layer1..4.{i}.conv{j}/bn{j}/downsample.{0,1}."""
+    """timm `resnet*` parameter layout: conv1/bn1, layer1..4.{i}.conv{j}/bn{j}/downsample.{0,1}.
+
+    The D / T members (resnet14t, resnet26t, resnet26d, resnet50d, ...) differ in two places, restated here from memory of timm
+    (timm is not available offline: parity unpinned, as for ConvNeXt):
+      stem=(c1, c2)  deep stem, conv1 = Sequential(Conv(3,c1,3,s2,p1), BN, ReLU, Conv(c1,c2,3,1,1), BN, ReLU, Conv(c2,64,3,1,1)) without
+                     bias, then bn1 / ReLU / max-pool as before: keys conv1.{0,3,6}.weight, conv1.{1,4}.*, bn1.*.  (24, 32) is the
+                     "tiered" stem of the T members, (32, 32) the D stem.
+      avg_down       projection shortcut = Sequential(AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False) in a stride-2 block /
+                     Identity in a stride-1 block, Conv 1x1 stride 1, BN): keys downsample.1.weight, downsample.2.* (index 0 holds
+                     no parameters).
+    The second and third stem convolution run on csrc/stem3.hip, the pool on nkb_avgpool2x2; everything else is the plain members' path."""
 
     family = "resnet"
 
-    def __init__(self, block, layers: Sequence[int], zero_init_last: bool = True):
+    def __init__(self, block, layers: Sequence[int], zero_init_last: bool = True, stem: Optional[Sequence[int]] = None,
+                 avg_down: bool = False):
         super().__init__()
-        self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
+        self.deep_stem, self.avg_down = stem is not None, avg_down
+        if stem is None:
+            self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
+        else:
+            c1, c2 = stem
+            self.conv1 = nn.Sequential(nn.Conv2d(3, c1, 3, 2, 1, bias=False), nn.BatchNorm2d(c1), nn.ReLU(inplace=True),
+                                       nn.Conv2d(c1, c2, 3, 1, 1, bias=False), nn.BatchNorm2d(c2), nn.ReLU(inplace=True),
+                                       nn.Conv2d(c2, 64, 3, 1, 1, bias=False))
         self.bn1 = nn.BatchNorm2d(64)
         inplanes = 64
         for i, (planes, n) in enumerate(zip((64, 128, 256, 512), layers)):
@@ -82,7 +100,11 @@ class HipResNet(_ParamOnly):
             for b in range(n):
                 s = stride if b == 0 else 1
                 down = None
-                if s != 1 or inplanes != planes * block.expansion:
+                if (s != 1 or inplanes != planes * block.expansion) and avg_down:
+                    pool = nn.AvgPool2d(2, s, ceil_mode=True, count_include_pad=False) if s != 1 else nn.Identity()
+                    down = nn.Sequential(pool, nn.Conv2d(inplanes, planes * block.expansion, 1, 1, bias=False),
+                                         nn.BatchNorm2d(planes * block.expansion))
+                elif s != 1 or inplanes != planes * block.expansion:
                     down = nn.Sequential(nn.Conv2d(inplanes, planes * block.expansion, 1, s, bias=False),
                                          nn.BatchNorm2d(planes * block.expansion))
                 blocks.append(block(inplanes, planes, s, down))
@@ -102,31 +124,58 @@ class HipResNet(_ParamOnly):
             for j, blk in enumerate(getattr(self, f"layer{i}")):
                 yield f"layer{i}.{j}", blk
 
+    def shortcut(self, blk):
+        """(pool or None, conv, bn) of a block's projection shortcut: downsample.{0,1} of the plain members, .{1,2} behind the
+        parameter-free pool / Identity of the avg_down members."""
+        ds = blk.downsample
+        if not self.avg_down:
+            return None, ds[0], ds[1]
+        return (ds[0] if isinstance(ds[0], nn.AvgPool2d) else None), ds[1], ds[2]
+
     def gemm_convs(self) -> List[nn.Conv2d]:
-        """Convolutions executed by the generic implicit-GEMM kernel (everything but the im2row stem)."""
-        out = []
+        """Convolutions that need a data-gradient filter (everything but the im2row stem convolution)."""
+        out = [self.conv1[3], self.conv1[6]] if self.deep_stem else []
         for _, blk in self.blocks():
             out += [c for c, _ in blk.stages()]
             if blk.downsample is not None:
-                out.append(blk.downsample[0])
+                out.append(self.shortcut(blk)[1])
         return out
 
     def stem_convs(self) -> List[nn.Conv2d]:
-        return [self.conv1]
+        return [self.conv1[0]] if self.deep_stem else [self.conv1]
+
+    def _deep_stem_forward(self, eng: HipEngine, img: torch.Tensor, train: bool) -> torch.Tensor:
+        """3x3/2 through im2row, then the two narrow 3x3/1 convolutions (csrc/stem3.hip); bn1 + ReLU + max-pool close the third."""
+        from . import hip
+        N, C, H, W = img.shape
+        c0, b0, _, c1, b1, _, c2 = self.conv1
+        P, Q = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
+        kp = eng.kpad(C * 9)
+        col = eng.ws.get("stem.col", (N, P, Q, kp), eng.T)
+        hip.im2row(eng.d, img, col, N, C, H, W, 3, 3, 2, 1, kp)
+        x = eng.conv_bn("stem0", col, c0, b0, True, None, train, col_input=True).view(N, P, Q, c0.out_channels)
+        x = eng.conv_bn("stem1", x, c1, b1, True, None, train)
+        x = eng.conv_bn("stem", x, c2, self.bn1, True, None, train, pool=_FUSED_STEM_TAIL)
+        if not _FUSED_STEM_TAIL:
+            x = eng.maxpool("pool", x, train)
+        return x
 
     # ---- execution plan ---------------------------------------------------------------
     def run_forward(self, eng: HipEngine, img: torch.Tensor, train: bool) -> torch.Tensor:
         from . import hip
         N, C, H, W = img.shape
         conv = self.conv1
-        R, st, pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        P, Q = (H + 2 * pad - R) // st + 1, (W + 2 * pad - R) // st + 1
         fused = _FUSED_STEM_TAIL
-        if eng.packed_stem(conv):
+        if self.deep_stem:
+            x = self._deep_stem_forward(eng, img, train)
+            fused = True                                   # (the helper has pooled already)
+        elif eng.packed_stem(conv):
             xp = eng.ws.get("stem.xp", (N, H, (W + 1) // 2 * 2, 4), eng.T)
             hip.stem_pack(eng.d, img, xp, N, C, H, W)
             x = eng.conv_bn("stem", xp, conv, self.bn1, True, None, train, pool=fused, stem_packed=(N, H, W))
         else:
+            R, st, pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+            P, Q = (H + 2 * pad - R) // st + 1, (W + 2 * pad - R) // st + 1
             kp = eng.kpad(C * R * R)
             col = eng.ws.get("stem.col", (N, P, Q, kp), eng.T)
             hip.im2row(eng.d, img, col, N, C, H, W, R, R, st, pad, kp)
@@ -145,16 +194,19 @@ class HipResNet(_ParamOnly):
             want_gram = (isinstance(blk, _Bottle) and bi + 1 < nblocks and train
                          and not eng.s2_classes(all_blocks[bi + 1][1].stages()[0][0]))
             proj = None
-            if blk.downsample is not None and want_gram and eng.gram_proj_ok(blk.downsample[0], stages[-1][0]):
-                proj = (blk.downsample[0], blk.downsample[1], inp, f"{name}.ds")     # rides inside the closing convolution
+            dpool, dconv, dbn = self.shortcut(blk) if blk.downsample is not None else (None, None, None)
+            if blk.downsample is not None and dpool is None and want_gram and eng.gram_proj_ok(dconv, stages[-1][0]):
+                proj = (dconv, dbn, inp, f"{name}.ds")     # rides inside the closing convolution
             elif blk.downsample is not None:
                 # projection shortcut: its BatchNorm is applied inside the closing stage's pass (never materialised);
                 # the convolution itself only depends on the block input, so it runs on the side stream next to the
                 # main branch (the forward pass has nothing else to overlap)
                 box = {}
 
-                def shortcut(key=f"{name}.ds", src=inp, ds=blk.downsample):
-                    box["r"] = eng.conv_bn(key, src, ds[0], ds[1], False, None, train, defer_apply=True)
+                def shortcut(key=f"{name}.ds", src=inp, pool=dpool, cv=dconv, bn=dbn):
+                    if pool is not None:                   # avg_down, stride-2 block: the 1x1 convolution reads the pooled map
+                        src = eng.avgpool2(key + "p", src, train)
+                    box["r"] = eng.conv_bn(key, src, cv, bn, False, None, train, defer_apply=True)
                 if _SIDE_SHORTCUT:
                     eng.on_side(shortcut)
                 else:
@@ -219,11 +271,13 @@ class HipResNet(_ParamOnly):
             elif blk.downsample is not None:
                 add_bits = None
                 gcd = eng.bn_backward(f"{name}.ds", g, "t5", g_bits=bits)
-                dconv = blk.downsample[0]
+                dpool, dconv, _ = self.shortcut(blk)
                 sub = dconv.stride[0] == 2 and dconv.kernel_size[0] == 1 and dconv.padding[0] == 0
                 add = eng.conv_backward(f"{name}.ds", gcd, "t6", subgrid=sub)
                 if sub:
                     add_hw = (add.shape[1], add.shape[2])
+                elif dpool is not None:                    # back through the pool: a full-grid `add` for conv1's data gradient
+                    add = eng.avgpool2_backward(f"{name}.dsp", add, "t7")
             # the gradient leaving this block is the output gradient of the previous block's closing stage: let the
             # epilogue that forms it also mask it and reduce it for that stage's BatchNorm backward
             g_stats = None
@@ -245,7 +299,15 @@ class HipResNet(_ParamOnly):
         else:
             g = eng.maxpool_backward("pool", g, "mp")
             gc = eng.bn_backward("stem", g, "t0")
-        eng.conv_backward("stem", gc, None)
+        if self.deep_stem:
+            # plain chain: narrow data gradient -> BatchNorm backward, twice; the three weight gradients go to the side stream
+            ga = eng.conv_backward("stem", gc, "a2")
+            gc = eng.bn_backward("stem1", ga, "c2")
+            ga = eng.conv_backward("stem1", gc, "a1")
+            gc = eng.bn_backward("stem0", ga.view(eng.saved["stem0"]["c"].shape), "c1")
+            eng.conv_backward("stem0", gc, None)
+        else:
+            eng.conv_backward("stem", gc, None)
         if on_done is not None:
             on_done(self.conv1)
             on_done(self.bn1)
@@ -257,6 +319,14 @@ _RESNETS = {
     "resnet50": (_Bottle, (3, 4, 6, 3)),
     "resnet101": (_Bottle, (3, 4, 23, 3)),
     "resnet152": (_Bottle, (3, 8, 36, 3)),
+    # deep 3x3 stem (T: 24-32-64 "tiered", D: 32-32-64) and average-pool projection shortcuts
+    "resnet14t": (_Bottle, (1, 1, 1, 1), dict(stem=(24, 32), avg_down=True)),
+    "resnet26t": (_Bottle, (2, 2, 2, 2), dict(stem=(24, 32), avg_down=True)),
+    "resnet26d": (_Bottle, (2, 2, 2, 2), dict(stem=(32, 32), avg_down=True)),
+    "resnet50d": (_Bottle, (3, 4, 6, 3), dict(stem=(32, 32), avg_down=True)),
+    "resnet18d": (_Basic, (2, 2, 2, 2), dict(stem=(32, 32), avg_down=True)),
+    "resnet34d": (_Basic, (3, 4, 6, 3), dict(stem=(32, 32), avg_down=True)),
+    "resnet101d": (_Bottle, (3, 4, 23, 3), dict(stem=(32, 32), avg_down=True)),
     # reduced members of the family used by the fast parity tests (same blocks, one per stage)
     "resnet_tiny_basic": (_Basic, (1, 1, 1, 1)),
     "resnet_tiny_bottleneck": (_Bottle, (1, 1, 1, 1)),
@@ -270,8 +340,8 @@ def create_backbone(name: str, pretrained: bool = False) -> nn.Module:
         raise RuntimeError(f"pretrained=True needs timm's weight hub, which this offline engine does not ship; "
                            f"load a timm-format state_dict through cfg.model['checkpoint'] instead ({name})")
     if key in _RESNETS:
-        blk, layers = _RESNETS[key]
-        return HipResNet(blk, layers)
+        blk, layers, *extra = _RESNETS[key]
+        return HipResNet(blk, layers, **(extra[0] if extra else {}))
     from .vit import create_vit
     m = create_vit(key)
     if m is None:

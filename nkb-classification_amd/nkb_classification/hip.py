@@ -130,6 +130,9 @@ _SIGS = {
     "nkb_dwconv_wgrad_workspace_floats": (i64, [i32] * 6),
     "nkb_layer_scale": (i32, [i32, i32, vp, vp, vp, vp, vp, i64, i32, vp, i64, vp]),
     "nkb_layer_scale_workspace_floats": (i64, [i64, i32]),
+    "nkb_stem3_tiles": (i32, [i32] * 6),
+    "nkb_stem3_conv": (i32, [i32, i32, vp, vp, vp, vp, vp] + [i32] * 10 + [vp]),
+    "nkb_avgpool2x2": (i32, [i32, i32, vp, vp, i32, i32, i32, i32, vp]),
     "nkb_prof_enable": (None, [i32]),
     "nkb_prof_collect": (i32, [vp, vp, vp, vp, i32]),
     "nkb_prof_collect_raw": (i32, [vp, vp, vp, vp, i32]),
@@ -188,7 +191,7 @@ _PURE = frozenset({"nkb_kernel_launches", "nkb_linear_gelu_fused_ok", "nkb_versi
                    "nkb_conv_wgrad_workspace_floats", "nkb_stem_wgrad_workspace_floats", "nkb_kernel_name",
                    "nkb_prof_enable", "nkb_prof_collect", "nkb_prof_collect_raw", "nkb_gemm8p_config", "nkb_gemm8p_ragged", "nkb_convp_config", "nkb_rowres_reserve_cus", "nkb_rowres_reserved_cus",
                    "nkb_fp8_job_blocks", "nkb_wgrad_fp8_workspace_floats", "nkb_dwconv_wgrad_workspace_floats",
-                   "nkb_layer_scale_workspace_floats",
+                   "nkb_layer_scale_workspace_floats", "nkb_stem3_tiles",
                    "nkb_fp8_quantize_colsum_workspace_floats",
                    "nkb_gram_bn_backward_workspace_floats", "nkb_bn_apply_gram_workspace_floats",
                    "nkb_plan_fn_count", "nkb_plan_fn_name", "nkb_plan_fn_args", "nkb_plan_max_args", "nkb_plan_entry_bytes",
@@ -450,9 +453,11 @@ def _device_allocs() -> int:
 def kernel_launches(which: str, reset: bool = False) -> int:
     """Launch count of a specialised kernel family: gemm8p, wgrad8p, wgrad3x3, wgrad8f, gram_conv, gram_bn_apply, convp, conv1p, stemp, gramr,
     wgradr, gemm8p_ragged (the ragged-row companion of a gemm8p launch), gemm_fp8 (the fp8 forms of the gemm8p core), dwconv (depthwise
-    convolution: forward, data and weight gradient), layer_scale."""
+    convolution: forward, data and weight gradient), layer_scale, stem3 (narrow 3x3 stem convolution: forward and data gradient), avgpool2
+    (2x2 average pool of the avg_down shortcut: forward and backward)."""
     idx = {"gemm8p": 0, "wgrad8p": 1, "wgrad3x3": 2, "wgrad8f": 3, "gram_conv": 4, "gram_bn_apply": 5, "convp": 6, "conv1p": 7,
-           "stemp": 8, "gramr": 9, "wgradr": 10, "gemm8p_ragged": 11, "gemm_fp8": 12, "dwconv": 13, "layer_scale": 14}[which]
+           "stemp": 8, "gramr": 9, "wgradr": 10, "gemm8p_ragged": 11, "gemm_fp8": 12, "dwconv": 13, "layer_scale": 14, "stem3": 15,
+           "avgpool2": 16}[which]
     return int(load().nkb_kernel_launches(idx, int(reset)))
 
 
@@ -1065,3 +1070,21 @@ def layer_scale(dtype, backward, z, a, gamma, out, rows, C_, dgamma=None, worksp
     """forward: out = a + gamma * z; backward: out = gamma * a (a: incoming gradient), dgamma += sum_m a * z."""
     check(load().nkb_layer_scale(dtype, int(backward), ptr(z), ptr(a), ptr(gamma), ptr(out), ptr(dgamma), rows, C_, ptr(workspace),
                                  workspace.numel() if workspace is not None else 0, stream()), "layer_scale")
+
+
+# ---- ResNet-D/T: narrow 3x3 stem convolutions (csrc/stem3.hip) and the 2x2 average pool of the avg_down shortcut ----
+def stem3_tiles(dtype, N, H, W, Cin, Cout) -> int:
+    """Partial-sum rows (= workgroups) of stem3_conv for this launch; 0: the channel pair is not served."""
+    return int(load().nkb_stem3_tiles(dtype, N, H, W, Cin, Cout))
+
+
+def stem3_conv(dtype, x, w, y, *, N, H, W, Cin, ldx, Cout, ldy, dgrad=False, bias=None, stats=None, relu=False, tiles=0, R=3):
+    """y = conv3x3/1/1(x, w) (+ bias) (ReLU); dgrad: w is the [Cin][3][3][Cout] data-gradient filter, its taps are read flipped.
+    stats: per-workgroup sums of the stored y and y^2, sized for `tiles` = stem3_tiles(...) rows."""
+    check(load().nkb_stem3_conv(dtype, int(dgrad), ptr(x), ptr(w), ptr(y), ptr(bias), ptr(stats), N, H, W, Cin, ldx, Cout, ldy, R,
+                                int(relu), int(tiles), stream()), "stem3_conv")
+
+
+def avgpool2x2(dtype, backward, src, dst, N, H, W, C_):
+    """AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False) on NHWC; backward: dst[N][H][W][C] = src[h/2][w/2] / count (written)."""
+    check(load().nkb_avgpool2x2(dtype, int(backward), ptr(src), ptr(dst), N, H, W, C_, stream()), "avgpool2x2")

@@ -295,6 +295,19 @@ class HipEngine:
         return (_PACKED_STEM and conv.kernel_size == (7, 7) and conv.stride == (2, 2) and conv.padding == (3, 3)
                 and conv.in_channels <= 4 and conv.bias is None and conv.groups == 1)
 
+    @staticmethod
+    def narrow3(w: torch.Tensor, st: int, pad: int) -> bool:
+        """3x3 / stride 1 / pad 1 with fewer than 64 channels on one side (the deep stem of the ResNet-D/T members): no generic kernel
+        takes these (Cin % 64), they run on csrc/stem3.hip or not at all."""
+        return w.dim() == 4 and w.shape[2] == 3 and w.shape[3] == 3 and st == 1 and pad == 1 and min(w.shape[0], w.shape[1]) < 64
+
+    def _stem3_tiles(self, N, H, W, ci, co) -> int:
+        tiles = hip.stem3_tiles(self.d, N, H, W, ci, co)
+        if not tiles:
+            raise RuntimeError(f"no kernel for a 3x3 convolution with {ci} -> {co} channels (csrc/stem3.hip serves 24->32, 32->32, "
+                               f"32->64 and their data gradients)")
+        return tiles
+
     def w_fwd(self, w: torch.Tensor) -> torch.Tensor:
         if id(w) in self._wpad:
             return self._wpad[id(w)]
@@ -332,6 +345,7 @@ class HipEngine:
             P, Q = (H + 2 * pad - R) // st + 1, (W + 2 * pad - S) // st + 1
             geom = dict(N=N, H=H, W=W, Cin=ci, ldx=ci, P=P, Q=Q, Cout=co, ldy=co, R=R, S=S, stride=st, pad=pad)
         rows = N * P * Q
+        narrow = not packed and not col_input and self.narrow3(w, st, pad)
         if not train and _EVAL_FOLD and not packed and not col_input and not pool:
             # eval fast path: filter * scale (running statistics) once per eval phase, then conv + shift (+ res) (+ ReLU)
             # in one launch; nothing is saved and the raw conv output is never written
@@ -347,7 +361,11 @@ class HipEngine:
                 ent = self._fold[key] = (self.fold_key, wf, shift)
             y = self.ws.get(key + ".y", (N, P, Q, co), self.T)
             assert res_affine is None or res_affine[0] is None
-            if w.dim() == 2 and self._splitk_ok(rows, ci, co) and res is None and not relu:
+            if narrow:
+                assert res is None
+                self._stem3_tiles(N, H, W, ci, co)
+                hip.stem3_conv(self.d, x, ent[1], y, N=N, H=H, W=W, Cin=ci, ldx=ci, Cout=co, ldy=co, bias=ent[2], relu=relu)
+            elif w.dim() == 2 and self._splitk_ok(rows, ci, co) and res is None and not relu:
                 S = 32                      # skinny Linear with a very long reduction: K-slices + one summing pass (see below)
                 part = self.ws.get(key + ".splitk", (S, rows, co), torch.float32)
                 hip.gemm_batched(self.d, x, ent[1], part, rows, co, ci // S, ci, ci, co, S, 1, (ci // S, 0), (ci // S, 0),
@@ -374,13 +392,16 @@ class HipEngine:
                 and R == 1 and S == 1 and st == 1 and pad == 0):
             tiles_1 = hip.conv1p_tiles(self.d, rows, ci, ci, co, co)
         tiles_s = hip.stemp_tiles(self.d, N, H, W, co) if (packed and train and _CONVP) else 0      # the stem through an LDS ring of image rows
-        if tiles_p or tiles_1 or tiles_s:
-            tiles = tiles_p or tiles_1 or tiles_s
+        tiles_3 = self._stem3_tiles(N, H, W, ci, co) if narrow else 0      # narrow 3x3 of the deep stem (csrc/stem3.hip)
+        if tiles_p or tiles_1 or tiles_s or tiles_3:
+            tiles = tiles_p or tiles_1 or tiles_s or tiles_3
         stats = self.ws.get(key + ".stats", (hip.bn_stats_floats(tiles, co),), torch.float32) if train else None
         if tiles_p:
             hip.convp_fwd(self.d, x, self.w_fwd(w), c, stats, N=N, H=H, W=W, Cin=ci, ldx=ci, Cout=co, ldy=co, tiles=tiles_p)
         elif tiles_1:
             hip.conv1p_fwd(self.d, x, self.w_fwd(w), c, stats, M=rows, Cin=ci, ldx=ci, Cout=co, ldy=co)
+        elif tiles_3:
+            hip.stem3_conv(self.d, x, self.w_fwd(w), c, N=N, H=H, W=W, Cin=ci, ldx=ci, Cout=co, ldy=co, stats=stats, tiles=tiles_3)
         elif tiles_s:
             hip.stemp_conv(self.d, x, self.w_fwd(w), c, stats, N, H, W, co, co)
         elif packed:
@@ -582,6 +603,21 @@ class HipEngine:
         if train:
             self.saved[key] = dict(idx=idx, in_shape=(N, H, W, C))
         return y
+
+    def avgpool2(self, key: str, x: torch.Tensor, train: bool) -> torch.Tensor:
+        """AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False): the pool in front of an avg_down projection shortcut."""
+        N, H, W, C = x.shape
+        y = self.ws.get(key + ".y", (N, (H + 1) // 2, (W + 1) // 2, C), self.T)
+        hip.avgpool2x2(self.d, False, x, y, N, H, W, C)
+        if train:
+            self.saved[key] = dict(in_shape=(N, H, W, C))
+        return y
+
+    def avgpool2_backward(self, key: str, g: torch.Tensor, slot: str) -> torch.Tensor:
+        N, H, W, C = self.saved[key]["in_shape"]
+        dx = self.scratch(slot, (N, H, W, C))
+        hip.avgpool2x2(self.d, True, g, dx, N, H, W, C)
+        return dx
 
     def avgpool(self, key: str, x: torch.Tensor) -> torch.Tensor:
         N, H, W, C = x.shape
@@ -913,6 +949,13 @@ class HipEngine:
                           ldx=geom["Cout"], P=1, Q=1, Cout=ci, ldy=ci)
             return dx
         dx = self.scratch(slot, (N, H, W, ci))
+        if self.narrow3(w, geom["stride"], geom["pad"]):
+            # deep-stem convolution: plain data gradient on the narrow kernel (flipped taps), no fused BatchNorm epilogue
+            assert fuse_bn is None and add is None and add_bits is None
+            co = geom["Cout"]
+            self._stem3_tiles(N, H, W, co, ci)
+            hip.stem3_conv(self.d, g_c, self._wd[id(w)], dx, N=N, H=H, W=W, Cin=co, ldx=co, Cout=ci, ldy=ci, dgrad=True)
+            return dx
         if self.s2_classes(conv) and id(w) in self._wd_cls:
             assert add_bits is None      # a stride-2 conv never sits under an identity shortcut
             co, P, Q = geom["Cout"], geom["P"], geom["Q"]

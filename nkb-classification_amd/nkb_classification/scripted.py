@@ -50,11 +50,16 @@ class _Bottleneck(nn.Module):
 
 
 class _ResNet(nn.Module):
-    def __init__(self, bottleneck: bool, layers):
+    def __init__(self, bottleneck: bool, layers, stem: Optional[List[int]] = None, avg_down: bool = False):
         super().__init__()
         exp = 4 if bottleneck else 1
         block = _Bottleneck if bottleneck else _BasicBlock
-        self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
+        if stem is None:
+            self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
+        else:                                              # deep stem of the D / T members
+            self.conv1 = nn.Sequential(nn.Conv2d(3, stem[0], 3, 2, 1, bias=False), nn.BatchNorm2d(stem[0]), nn.ReLU(),
+                                       nn.Conv2d(stem[0], stem[1], 3, 1, 1, bias=False), nn.BatchNorm2d(stem[1]), nn.ReLU(),
+                                       nn.Conv2d(stem[1], 64, 3, 1, 1, bias=False))
         self.bn1 = nn.BatchNorm2d(64)
         self.maxpool = nn.MaxPool2d(3, 2, 1)
         inplanes = 64
@@ -63,7 +68,10 @@ class _ResNet(nn.Module):
             for b in range(n):
                 stride = 2 if (b == 0 and li > 0) else 1
                 ds = None
-                if b == 0 and (stride != 1 or inplanes != planes * exp):
+                if b == 0 and (stride != 1 or inplanes != planes * exp) and avg_down:
+                    pool: nn.Module = nn.AvgPool2d(2, stride, ceil_mode=True, count_include_pad=False) if stride != 1 else nn.Identity()
+                    ds = nn.Sequential(pool, nn.Conv2d(inplanes, planes * exp, 1, 1, bias=False), nn.BatchNorm2d(planes * exp))
+                elif b == 0 and (stride != 1 or inplanes != planes * exp):
                     ds = nn.Sequential(nn.Conv2d(inplanes, planes * exp, 1, stride, bias=False), nn.BatchNorm2d(planes * exp))
                 blocks.append(block(inplanes, planes, stride, ds))
                 inplanes = planes * exp
@@ -288,7 +296,10 @@ def _backbone_like(hip_backbone) -> nn.Module:
         return _ConvNeXt(list(hip_backbone.depths), list(hip_backbone.dims))
     layers = [len(getattr(hip_backbone, f"layer{i}")) for i in (1, 2, 3, 4)]
     bottleneck = hasattr(getattr(hip_backbone, "layer1")[0], "conv3")
-    return _ResNet(bottleneck, layers)
+    stem = None
+    if getattr(hip_backbone, "deep_stem", False):
+        stem = [hip_backbone.conv1[0].out_channels, hip_backbone.conv1[3].out_channels]
+    return _ResNet(bottleneck, layers, stem, bool(getattr(hip_backbone, "avg_down", False)))
 
 
 def build_scriptable(hip_model) -> nn.Module:
