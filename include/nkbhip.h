@@ -33,10 +33,28 @@ typedef struct ihipStream_t* nkb_stream_t; /* hipStream_t */
 
 const char* nkb_last_error(void);
 int nkb_version(void);
-/* Launch counters of the specialised kernels since process start (or the last reset): which = 0 eight-phase GEMM (gemm8p), 1 eight-phase
- * weight gradient (wgrad8p / wgrad256), 2 shared-strip 3x3 weight gradient, 3 fp8 weight gradient, 4 Gram-form closing convolution,
- * 5 bn_apply fused with the Gram matrix, 6 row-balanced 3x3 core (convp), 7 pixel-resident 1x1 expansion (conv1p), 8 ring-buffered stem
- * (stemp: forward and weight gradient), 9 streamed g^T a (gramr), 10 row-streaming 256 x 128-tile 1x1 weight gradient (wgradr), 13 depthwise convolution (dwconv: forward, data and weight gradient), 14 layer scale, 15 narrow 3x3 stem convolution (stem3: forward and data gradient), 16 2x2 average pool (forward and backward).  Tests use them to prove that a benchmark configuration took the path it is priced on. */
+/* Launch counters of the specialised kernels since process start (or the last reset): `which` of nkb_kernel_launches.  Tests use
+ * them to prove that a benchmark configuration took the path it is priced on.  A new family appends a name here and passes it to
+ * nkb_count_launch (csrc/common.h); nkb_classification/hip.py:kernel_launches reads its string keys off this enum. */
+enum NkbLaunchCounter {
+    NKB_LAUNCH_GEMM8P = 0,         /* eight-phase 256 x 256 GEMM core (csrc/gemm8p.hip) */
+    NKB_LAUNCH_WGRAD8P = 1,        /* eight-phase weight gradient (wgrad8p / wgrad256) */
+    NKB_LAUNCH_WGRAD3X3 = 2,       /* shared-strip 3x3 weight gradient */
+    NKB_LAUNCH_WGRAD8F = 3,        /* fp8 weight gradient */
+    NKB_LAUNCH_GRAM_CONV = 4,      /* Gram-form closing convolution (nkb_conv_affine_residual / nkb_conv_cat_relu_bits) */
+    NKB_LAUNCH_GRAM_BN_APPLY = 5,  /* bn_apply fused with the Gram matrix */
+    NKB_LAUNCH_CONVP = 6,          /* row-balanced 3x3 core (convp) */
+    NKB_LAUNCH_CONV1P = 7,         /* pixel-resident 1x1 expansion (conv1p) */
+    NKB_LAUNCH_STEMP = 8,          /* ring-buffered stem (stemp: forward and weight gradient) */
+    NKB_LAUNCH_GRAMR = 9,          /* streamed g^T a (gramr) */
+    NKB_LAUNCH_WGRADR = 10,        /* row-streaming 256 x 128-tile 1x1 weight gradient (wgradr) */
+    NKB_LAUNCH_GEMM8P_RAGGED = 11, /* ragged-row companion of a gemm8p launch */
+    NKB_LAUNCH_GEMM_FP8 = 12,      /* fp8 forms of the gemm8p core */
+    NKB_LAUNCH_DWCONV = 13,        /* depthwise convolution (dwconv: forward, data and weight gradient) */
+    NKB_LAUNCH_LAYER_SCALE = 14,   /* layer scale */
+    NKB_LAUNCH_STEM3 = 15,         /* narrow 3x3 stem convolution (stem3: forward and data gradient) */
+    NKB_LAUNCH_AVGPOOL2 = 16       /* 2x2 average pool of the avg_down shortcut (forward and backward) */
+};
 long long nkb_kernel_launches(int which, int reset);
 
 /* Implicit-GEMM convolution / linear layer on MFMA.

@@ -125,9 +125,8 @@ extern "C" int nkb_prof_collect_raw(int* kid, double* ms, double* work, double* 
 }
 
 extern "C" const char* nkb_kernel_name(int kid) {
-    static const char* names[] = {"conv_igemm_fwd", "conv_igemm_dgrad", "conv_wgrad", "bn_apply", "bn_bwd_reduce",
-                                  "bn_bwd_apply", "bn_finalize", "maxpool", "avgpool", "im2row", "wprep", "loss",
-                                  "optim", "misc", "layernorm", "attention", "gelu", "wgrad_reduce", "dwconv_fwd", "dwconv_dgrad",
-                                  "dwconv_wgrad", "layer_scale", "stem3_fwd", "stem3_dgrad", "avgpool2x2"};
+#define NKB_KERNEL_ID_NAME(id, name) name,
+    static const char* const names[NKB_K_COUNT] = {NKB_KERNEL_IDS(NKB_KERNEL_ID_NAME)};
+#undef NKB_KERNEL_ID_NAME
     return (kid >= 0 && kid < NKB_K_COUNT) ? names[kid] : "?";
 }

@@ -3,9 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
-
-#define NKB_DT_F32 0
-#define NKB_DT_BF16 1
+#include "nkbhip.h"   // the public C ABI: every extern "C" definition is compiled against its prototype (and NKB_DT_*, NkbLaunchCounter)
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(8))) short bf16x8;   // 8 packed bf16 (4 VGPRs)
@@ -110,9 +108,7 @@ int nkb_launch_wgrad_reduce(const float* part, long long slab, int splits, float
 int nkb_launch_wgrad_reduce2(const float* part, long long slab, int splits, float* dst, long long n, const float* part2, long long slab2,
                              float* dst2, long long n2, bool assign, hipStream_t stream);
 
-// launch counters of the specialised kernels (api.hip: nkb_kernel_launches) — tests assert from them that the path a benchmark
-// configuration is supposed to take really ran (0 gemm8p, 1 wgrad8p / wgrad256, 2 wgrad3x3, 3 wgrad8f (fp8), 4 Gram-form closing
-// stage (nkb_conv_affine_residual), 5 bn_apply fused with the Gram matrix, ..., 15 narrow 3x3 stem convolution (stem3), 16 2x2 average pool)
+// bumps a launch counter of nkb_kernel_launches (api.hip); which: an NkbLaunchCounter of include/nkbhip.h
 void nkb_count_launch(int which);
 
 // per-launch HIP-event profiler (enabled from bench.py); see api.hip
@@ -122,9 +118,34 @@ struct NkbProfScope {
     NkbProfScope(int kernel_id, hipStream_t s, double work, double bytes = 0.0);   // algorithmic FLOPs / bytes of the launch
     ~NkbProfScope();
 };
-enum NkbKernelId {
-    NKB_K_CONV_FWD = 0, NKB_K_CONV_DGRAD, NKB_K_CONV_WGRAD, NKB_K_BN_APPLY, NKB_K_BN_BWD_REDUCE, NKB_K_BN_BWD_APPLY,
-    NKB_K_BN_FINALIZE, NKB_K_MAXPOOL, NKB_K_AVGPOOL, NKB_K_IM2COL, NKB_K_WPREP, NKB_K_LOSS, NKB_K_OPTIM, NKB_K_MISC,
-    NKB_K_LN, NKB_K_ATTN, NKB_K_GELU, NKB_K_WGRAD_REDUCE, NKB_K_DWCONV_FWD, NKB_K_DWCONV_DGRAD, NKB_K_DWCONV_WGRAD,
-    NKB_K_LAYER_SCALE, NKB_K_STEM3_FWD, NKB_K_STEM3_DGRAD, NKB_K_AVGPOOL2, NKB_K_COUNT
-};
+// Profiler kernel ids and the names nkb_kernel_name reports for them (profiles and tests key on both): one row per id, in id order.
+// A new id is appended; the enum below and the name table in api.hip are both expansions of this list.
+#define NKB_KERNEL_IDS(X) \
+    X(NKB_K_CONV_FWD, "conv_igemm_fwd") \
+    X(NKB_K_CONV_DGRAD, "conv_igemm_dgrad") \
+    X(NKB_K_CONV_WGRAD, "conv_wgrad") \
+    X(NKB_K_BN_APPLY, "bn_apply") \
+    X(NKB_K_BN_BWD_REDUCE, "bn_bwd_reduce") \
+    X(NKB_K_BN_BWD_APPLY, "bn_bwd_apply") \
+    X(NKB_K_BN_FINALIZE, "bn_finalize") \
+    X(NKB_K_MAXPOOL, "maxpool") \
+    X(NKB_K_AVGPOOL, "avgpool") \
+    X(NKB_K_IM2COL, "im2row") \
+    X(NKB_K_WPREP, "wprep") \
+    X(NKB_K_LOSS, "loss") \
+    X(NKB_K_OPTIM, "optim") \
+    X(NKB_K_MISC, "misc") \
+    X(NKB_K_LN, "layernorm") \
+    X(NKB_K_ATTN, "attention") \
+    X(NKB_K_GELU, "gelu") \
+    X(NKB_K_WGRAD_REDUCE, "wgrad_reduce") \
+    X(NKB_K_DWCONV_FWD, "dwconv_fwd") \
+    X(NKB_K_DWCONV_DGRAD, "dwconv_dgrad") \
+    X(NKB_K_DWCONV_WGRAD, "dwconv_wgrad") \
+    X(NKB_K_LAYER_SCALE, "layer_scale") \
+    X(NKB_K_STEM3_FWD, "stem3_fwd") \
+    X(NKB_K_STEM3_DGRAD, "stem3_dgrad") \
+    X(NKB_K_AVGPOOL2, "avgpool2x2")
+#define NKB_KERNEL_ID_ENUM(id, name) id,
+enum NkbKernelId { NKB_KERNEL_IDS(NKB_KERNEL_ID_ENUM) NKB_K_COUNT };
+#undef NKB_KERNEL_ID_ENUM

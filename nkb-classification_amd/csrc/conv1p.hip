@@ -429,7 +429,7 @@ extern "C" int nkb_conv1p_fwd(int dtype, const void* x, const void* w, void* y, 
     const double flops = 2.0 * (double)M * Cout * Cin;
     const double bytes = ((double)M * Cin + (double)Cout * Cin + (double)M * Cout) * 2;
     NkbProfScope prof(NKB_K_CONV_FWD, stream, flops, bytes);
-    nkb_count_launch(7);
+    nkb_count_launch(NKB_LAUNCH_CONV1P);
 #define C1_GO(KT_, NP_) case NP_: c1_launch<KT_, NP_>(p, g.lds, stream); break;
 #define C1_GS(NP_) case NP_: c1_launch_stream<NP_>(p, g.lds, stream); break;
     if (g.stream) { switch (g.np) { C1_GS(1) C1_GS(2) C1_GS(3) C1_GS(4) C1_GS(5) C1_GS(6) C1_GS(7) default: break; } }

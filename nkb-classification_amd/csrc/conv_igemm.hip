@@ -1411,7 +1411,7 @@ extern "C" int nkb_conv_affine_residual(int dtype, const void* x, const void* w,
     ConvParams p = conv_geometry(N, H, W, Cin, ldx, P, Q, Cout, ldy, R, S, stride, pad, 0);
     p.x = x; p.w = w; p.y = y; p.add = res; p.ldadd = ldres; p.bias = shift; p.relu = 1;
     p.oscale = scale; p.add_scale = res_scale; p.add_shift = res_shift; p.out_bits = relu_bits;
-    nkb_count_launch(4);
+    nkb_count_launch(NKB_LAUNCH_GRAM_CONV);
     NkbProfScope prof(NKB_K_CONV_FWD, stream, 2.0 * p.M * (double)Cout * R * S * Cin,
                       ((double)N * H * W * Cin + (double)Cout * R * S * Cin + 2.0 * p.M * Cout) * 2 + (double)p.M * Cout / 8);
     return launch_conv<EPI_AFFINE_BITS>(p, dtype, false, stream);
@@ -1431,7 +1431,7 @@ extern "C" int nkb_conv_cat_relu_bits(int dtype, const void* a, int lda, int K1,
     ConvParams p = gemm_geometry((int)M, K1 + K2, Cout, lda, K1 + K2, ldy);
     p.x = a; p.w = wf; p.y = y; p.bias = shift; p.relu = 1; p.out_bits = relu_bits;
     p.x2 = x; p.ldx2 = ldx; p.kt2 = K1 / 64;
-    nkb_count_launch(4);
+    nkb_count_launch(NKB_LAUNCH_GRAM_CONV);
     NkbProfScope prof(NKB_K_CONV_FWD, stream, 2.0 * M * (double)Cout * (K1 + K2),
                       ((double)M * (K1 + K2) + (double)Cout * (K1 + K2) + (double)M * Cout) * 2 + (double)M * Cout / 8);
     return launch_conv<EPI_AFFINE_BITS>(p, dtype, false, stream);

@@ -1122,7 +1122,7 @@ static int g_cp_reserve = 0;
 extern "C" void nkb_rowres_reserve_cus(int cus) { g_cp_reserve = cus < 0 ? 0 : (cus > 128 ? 128 : cus); }
 extern "C" int nkb_rowres_reserved_cus() { return g_cp_reserve; }
 // forms 4 (conv1p.hip), 5 (stemp.hip) and 6 (gramr.hip) ask here
-extern "C" int nkb_convp_form_enabled(int form) {
+int nkb_convp_form_enabled(int form) {
     if (!g_cp_on) return 0;
     return form == 4 ? !g_cp_no1p : (form == 5 ? !g_cp_nostem : (form == 6 ? !g_cp_nogr : 1));
 }
@@ -1187,7 +1187,7 @@ static int convp_launch(int kind, const void* x, const void* w, void* y, const v
     const double flops = 2.0 * p.M * (double)Cout * 9 * Cin;
     const double bytes = ((double)p.M * Cin + (double)Cout * 9 * Cin + (double)p.M * Cout * (kind == 1 ? 2 : 1)) * 2;
     NkbProfScope prof(kind == 0 ? NKB_K_CONV_FWD : NKB_K_CONV_DGRAD, stream, flops, bytes);
-    nkb_count_launch(6);
+    nkb_count_launch(NKB_LAUNCH_CONVP);
     const dim3 grid((unsigned)(g.nwgm * g.tilesN)), block(512);
     if (g.tc == 64) {
         if (W == 56) {                                          // the one-stage halo form is compiled for 56-pixel rows

@@ -205,7 +205,7 @@ extern "C" int nkb_dwconv(int dtype, int dgrad, const void* x, const float* w, c
     else
         hipLaunchKernelGGL(dwconv_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, stream, (const float*)x, w, bias, (const float*)add, (float*)y, H, W, C,
                            ldx, ldy, g.strips, g.chunks, g.rpc, dgrad ? 1 : 0, units);
-    nkb_count_launch(13);
+    nkb_count_launch(NKB_LAUNCH_DWCONV);
     return nkb_check_launch("dwconv");
 }
 
@@ -245,7 +245,7 @@ extern "C" int nkb_dwconv_wgrad(int dtype, const void* g, const void* x, float* 
             hipLaunchKernelGGL(dwconv_wgrad_kernel<float>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, (const float*)g,
                                (const float*)x, workspace, part_b, H, W, C, ldg, ldx, gm.strips, gm.chunks, gm.rpc, splits, gm.items);
         rc = nkb_check_launch("dwconv_wgrad");
-        nkb_count_launch(13);
+        nkb_count_launch(NKB_LAUNCH_DWCONV);
     }
     if (rc) return rc;
     NkbProfScope prof(NKB_K_WGRAD_REDUCE, stream, 0, 4.0 * ((double)splits + 2.0) * (DW_R * DW_R + 1) * C);
@@ -358,7 +358,7 @@ extern "C" int nkb_layer_scale(int dtype, int backward, const void* z, const voi
         else { if (backward) LS_LAUNCH(float, true); else LS_LAUNCH(float, false); }
 #undef LS_LAUNCH
         rc = nkb_check_launch("layer_scale");
-        nkb_count_launch(14);
+        nkb_count_launch(NKB_LAUNCH_LAYER_SCALE);
     }
     if (rc || !dgamma) return rc;
     NkbProfScope prof(NKB_K_WGRAD_REDUCE, stream, 0, 4.0 * ((double)blocks + 2.0) * C);

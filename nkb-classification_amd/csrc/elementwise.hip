@@ -765,7 +765,7 @@ extern "C" int nkb_avgpool2x2(int dtype, int backward, const void* in, void* out
     const int P = (H + 1) / 2, Q = (W + 1) / 2;
     const double esz = dtype == NKB_DT_BF16 ? 2.0 : 4.0;
     NkbProfScope prof(NKB_K_AVGPOOL2, stream, 0, esz * C * ((double)N * H * W + (double)N * P * Q));
-    nkb_count_launch(16);
+    nkb_count_launch(NKB_LAUNCH_AVGPOOL2);
     const size_t total = backward ? (size_t)N * H * W * (C / n) : (size_t)N * P * Q * (C / n);
     if (dtype == NKB_DT_BF16) {
         if (!backward) hipLaunchKernelGGL(avgpool2x2_fwd_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, stream, (const bf16_t*)in, (bf16_t*)out, N, H, W, C, P, Q);

@@ -1282,14 +1282,14 @@ static bool g8_launch_ragged(const G8Params& p, int M0, int R, hipStream_t strea
     q.aux_kind = p.aux ? 1 + p.aux_mode : 0; q.S = S;
     q.slab = slabs; q.ticket = tickets;
     const dim3 grid((unsigned)blocks, (unsigned)S);
-    nkb_count_launch(11);
+    nkb_count_launch(NKB_LAUNCH_GEMM8P_RAGGED);
     if (R <= 64) hipLaunchKernelGGL(gemm8p_ragged_kernel<1>, grid, dim3(512), 0, stream, q);
     else hipLaunchKernelGGL(gemm8p_ragged_kernel<2>, grid, dim3(512), 0, stream, q);
     return true;
 }
 
 int nkb_launch_gemm8p(const ConvParams& cp, hipStream_t stream, const float* row_scale, int rows_per_sample) {
-    nkb_count_launch(0);
+    nkb_count_launch(NKB_LAUNCH_GEMM8P);
     G8Params p;
     p.x = (const bf16_t*)cp.x; p.w = (const bf16_t*)cp.w; p.y = (bf16_t*)cp.y; p.bias = cp.bias;
     p.add = (const bf16_t*)cp.add; p.aux = (cp.act == 4 || cp.act == 3) ? (const bf16_t*)cp.aux : nullptr; p.stats = cp.stats;
@@ -1389,7 +1389,7 @@ extern "C" int nkb_gemm_fp8(int mode, const void* xq, const void* wq, void* y, c
     NkbProfScope prof(mode == 0 ? NKB_K_CONV_FWD : NKB_K_CONV_DGRAD, stream, 2.0 * M * (double)N * K);
     p.stagger = g8_stagger(tiles, cus, K / 128);
     const dim3 grid((unsigned)g8_grid(tiles, cus));
-    nkb_count_launch(12);
+    nkb_count_launch(NKB_LAUNCH_GEMM_FP8);
     if (yq) {
         if (mode == 0) hipLaunchKernelGGL((gemm8p_kernel<true, 1, true>), grid, dim3(512), lds, stream, p);
         else hipLaunchKernelGGL((gemm8p_kernel<true, 2, true>), grid, dim3(512), lds, stream, p);

@@ -204,7 +204,7 @@ extern "C" int nkb_gramr(int dtype, const void* g, int ldg, const void* a, int l
     p.rows_per_wg = gg.rows; p.nwg = gg.nwg; p.transposed = (mode >> 1) & 1;
     {
         NkbProfScope prof(NKB_K_CONV_WGRAD, stream, 2.0 * (double)M * co * ci, ((double)M * (co + ci)) * 2);
-        nkb_count_launch(9);
+        nkb_count_launch(NKB_LAUNCH_GRAMR);
         if (co == 256) gr_launch<256, 64>(p, stream); else gr_launch<512, 128>(p, stream);
         if (int rc = nkb_check_launch("gramr")) return rc;
     }

@@ -4,17 +4,13 @@
 // the event / stream operations between them) and replays them every step.  The replay loop used to be Python: one ctypes
 // call per entry, 5-14 ms of host time per step.  Here the same flat table is walked in C: one call from Python per
 // segment (a segment ends where a Python-side operation sits between launches — the DDP bucket hooks, a counter bump).
-// The call table (plan_dispatch.inc) is generated from the binding's own signature table, so every entry point is called
-// through a prototype with exactly the argument types it was recorded with; there is no variadic or ABI-level trampoline.
+// The call table (plan_dispatch.inc) is generated from include/nkbhip.h, which this file includes: every entry point is called
+// through its public prototype, each argument cast to the declared parameter type; there is no variadic or ABI-level trampoline.
+// NkbPlanArg / NkbPlanEntry and the NKB_PLAN_* operation codes are the header's.
 #include <hip/hip_runtime.h>
-#include <stddef.h>
+#include "nkbhip.h"
 
 void nkb_set_error(const char* fmt, ...);
-
-typedef union { void* p; long long i; float f; } NkbPlanArg;
-#define NKB_PLAN_MAX_ARGS 32
-typedef struct { int fn; int nargs; NkbPlanArg a[NKB_PLAN_MAX_ARGS]; } NkbPlanEntry;
-enum { NKB_PLAN_EVENT_RECORD = -1, NKB_PLAN_STREAM_WAIT_EVENT = -2, NKB_PLAN_MEMSET = -3 };
 
 #include "plan_dispatch.inc"
 

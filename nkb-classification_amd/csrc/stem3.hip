@@ -292,7 +292,7 @@ extern "C" int nkb_stem3_conv(int dtype, int dgrad, const void* x, const void* w
     (void)once;
     const double M = (double)N * H * W, esz = dtype == NKB_DT_BF16 ? 2.0 : 4.0;
     NkbProfScope prof(dgrad ? NKB_K_STEM3_DGRAD : NKB_K_STEM3_FWD, stream, 2.0 * M * 9 * Cin * Cout, esz * M * (Cin + Cout));
-    nkb_count_launch(15);
+    nkb_count_launch(NKB_LAUNCH_STEM3);
 #define S3_GO(CI, CO)                                                                                                         \
     if (Cin == CI && Cout == CO) {                                                                                            \
         if (dtype == NKB_DT_BF16) hipLaunchKernelGGL((stem3_kernel<bf16_t, CI, CO>), dim3(g.grid), dim3(256), g.lds, stream, p); \

@@ -497,7 +497,7 @@ extern "C" int nkb_stemp_conv(int dtype, const void* xp, const void* wp, void* y
     (void)once;
     const double M = (double)N * g.P * g.Q;
     NkbProfScope prof(NKB_K_CONV_FWD, stream, 2.0 * M * 64 * 147, ((double)N * H * g.Wp * 4 + M * 64) * 2);
-    nkb_count_launch(8);
+    nkb_count_launch(NKB_LAUNCH_STEMP);
     if (g.Q == 112) hipLaunchKernelGGL(stemp_kernel<7>, dim3((unsigned)g.nwg), dim3(512), g.lds, stream, p);       // 224-pixel rows
     else hipLaunchKernelGGL(stemp_kernel<0>, dim3((unsigned)g.nwg), dim3(512), g.lds, stream, p);
     return nkb_check_launch("stemp_conv");
@@ -541,7 +541,7 @@ extern "C" int nkb_stemp_wgrad(int dtype, const void* dy, const void* xp, float*
     const double M = (double)N * g.P * g.Q;
     {
         NkbProfScope prof(NKB_K_CONV_WGRAD, stream, 2.0 * M * 64 * 224, ((double)N * H * g.Wp * 4 + M * 64) * 2);
-        nkb_count_launch(8);
+        nkb_count_launch(NKB_LAUNCH_STEMP);
         switch (p.ks) {
 #define SW_GO(K) case K: hipLaunchKernelGGL(stempw_kernel<K>, dim3((unsigned)g.nwg), dim3(512), lds, stream, p); break;
             SW_GO(1) SW_GO(2) SW_GO(3) SW_GO(4) SW_GO(5) SW_GO(6) SW_GO(7) SW_GO(8)

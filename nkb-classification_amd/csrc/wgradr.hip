@@ -310,7 +310,7 @@ int nkb_launch_wgradr(const void* dy, const void* x, float* dw, float* dbias, lo
                       float* workspace, bool assign, hipStream_t stream) {
     WRPlan g;
     if (!wr_plan(M, Cin, Cout, dbias != nullptr, g)) { nkb_set_error("wgradr: shape not eligible (M=%lld Cin=%d Cout=%d)", M, Cin, Cout); return 1; }
-    nkb_count_launch(10);
+    nkb_count_launch(NKB_LAUNCH_WGRADR);
     WRParams p;
     p.g = (const bf16_t*)(g.transposed ? x : dy); p.ldg = g.transposed ? ldx : lddy;
     p.a = (const bf16_t*)(g.transposed ? dy : x); p.lda = g.transposed ? lddy : ldx;

@@ -11,139 +11,18 @@ from pathlib import Path
 
 import torch
 
+from . import cabi
+
 F32, BF16 = 0, 1
 _TORCH_DT = {torch.float32: F32, torch.bfloat16: BF16}
 
 _LIB = None
 _LIB_PATH = Path(__file__).resolve().parents[1] / "lib" / "libnkbhip.so"
 
-vp, i32, i64, f32, sz = C.c_void_p, C.c_int, C.c_longlong, C.c_float, C.c_size_t
-
-_SIGS = {
-    "nkb_version": (i32, []),
-    "nkb_last_error": (C.c_char_p, []),
-    "nkb_kernel_launches": (i64, [i32, i32]),
-    "nkb_conv_gemm": (i32, [i32, i32, vp, vp, vp, vp, vp, vp] + [i32] * 18 + [vp, vp]),
-    "nkb_conv_gemm_stat_tiles": (i32, [i32, i32, i32]),
-    "nkb_conv_wgrad": (i32, [i32, vp, vp, vp, vp] + [i32] * 13 + [vp, i64, vp]),
-    "nkb_conv_wgrad_assign": (i32, [i32, vp, vp, vp, vp] + [i32] * 13 + [vp, i64, vp]),
-    "nkb_conv_wgrad_workspace_floats": (i64, [i32] * 11),
-    "nkb_stem_wgrad_workspace_floats": (i64, [i32] * 5),
-    "nkb_bn_finalize": (i32, [vp, i32, i32, i64, vp, vp, vp, vp, f32, f32, i32, vp, vp, vp, vp, vp]),
-    "nkb_bn_apply": (i32, [i32, vp, vp, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp]),
-    "nkb_bn_backward": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, sz, vp]),
-    "nkb_bn_stats_floats": (sz, [i32, i32]),
-    "nkb_bn_backward_workspace_floats": (sz, [i64, i32]),
-    "nkb_conv_dgrad_bn": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, i32] + [i32] * 13 + [vp]),
-    "nkb_convp_tiles": (i32, [i32] * 13),
-    "nkb_conv1p_tiles": (i32, [i32, i64, i32, i32, i32, i32]),
-    "nkb_conv1p_fwd": (i32, [i32, vp, vp, vp, vp, i64, i32, i32, i32, i32, vp]),
-    "nkb_rowres_reserve_cus": (None, [i32]),
-    "nkb_rowres_reserved_cus": (i32, []),
-    "nkb_convp_config": (None, [i32, i32]),
-    "nkb_convp_fwd": (i32, [i32, vp, vp, vp, vp] + [i32] * 8 + [vp]),
-    "nkb_convp_dgrad_bn": (i32, [i32] + [vp] * 8 + [i32] * 8 + [vp]),
-    "nkb_conv_dgrad_s2class": (i32, [i32] + [vp] * 9 + [i32] * 14 + [vp]),
-    "nkb_bn_backward_from_stats": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp]),
-    "nkb_gram_bn_stats": (i32, [i32, vp, vp, vp, i64, i32, i32, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "nkb_bn_apply_gram": (i32, [i32, vp, vp, vp, vp, i64, i32, vp, vp, sz, vp]),
-    "nkb_bn_apply_gram_workspace_floats": (sz, [i64, i32]),
-    "nkb_conv_affine_residual": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp] + [i32] * 13 + [vp]),
-    "nkb_gram_bn_backward": (i32, [i32, vp, vp, vp, vp, vp, i32, i64, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
-    "nkb_gram_k1w": (i32, [i32, vp, vp, i32, i32, vp, vp]),
-    "nkb_conv_dgrad_bn_add": (i32, [i32, vp, i32, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]),
-    "nkb_gram_bn_backward_workspace_floats": (sz, [i32, i32]),
-    "nkb_gram_fold2": (i32, [i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp]),
-    "nkb_conv_cat_relu_bits": (i32, [i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, i64, i32, i32, vp]),
-    "nkb_conv_cat_bias": (i32, [i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, i64, i32, i32, vp]),
-    "nkb_conv_dgrad_bn_cat": (i32, [i32, vp, i32, i32, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, i32, vp]),
-    "nkb_wprep_multi": (i32, [i32, vp, vp, i32, i32, vp, vp]),
-    "nkb_wprep_block_elems": (i32, []),
-    "nkb_wprep_job_blocks": (i64, [i32, i32, i32, i32, i32]),
-    "nkb_stem_pack": (i32, [i32, vp, vp, i32, i32, i32, i32, vp]),
-    "nkb_stemp_tiles": (i32, [i32, i32, i32, i32, i32]),
-    "nkb_stemp_wgrad_workspace_floats": (i64, [i32, i32, i32, i32, i32]),
-    "nkb_stemp_wgrad": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp]),
-    "nkb_gramr_workspace_floats": (i64, [i32, i64, i32, i32]),
-    "nkb_gramr": (i32, [i32, vp, i32, vp, i32, vp, i64, i32, i32, i32, vp, i64, vp]),
-    "nkb_stemp_conv": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "nkb_stem_wprep": (i32, [i32, vp, vp, i32, i32, vp]),
-    "nkb_stem_weight_cols": (i32, [i32]),
-    "nkb_stem_conv": (i32, [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "nkb_stem_wgrad": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp]),
-    "nkb_stem_wfold": (i32, [i32, vp, vp, i32, i32, vp]),
-    "nkb_maxpool3x3s2": (i32, [i32, i32, vp, vp, vp, i32, i32, i32, i32, vp]),
-    "nkb_bn_relu_maxpool": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, i32, i32, i32, i32, vp]),
-    "nkb_bn_relu_maxpool_sel": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, i32, i32, i32, i32, vp]),
-    "nkb_bn_relu_maxpool_workspace_floats": (sz, [i32, i32, i32, i32]),
-    "nkb_avgpool": (i32, [i32, i32, vp, vp, i32, i32, i32, vp]),
-    "nkb_im2row": (i32, [i32, vp, vp] + [i32] * 9 + [vp]),
-    "nkb_wprep": (i32, [i32, vp, vp, i32, i32, i32, i32, i32, vp]),
-    "nkb_add2d": (i32, [vp, vp, i32, i32, i32, i32, vp]),
-    "nkb_colsum": (i32, [i32, vp, vp, i32, i32, i32, vp]),
-    "nkb_pad_cast": (i32, [i32, vp, vp, i32, i32, i32, i32, f32, vp]),
-    "nkb_gemm_batched": (i32, [i32, vp, vp, vp] + [i32] * 8 + [i64] * 6 + [i32, vp]),
-    "nkb_gemm_tn_batched": (i32, [i32, vp, vp, vp] + [i32] * 8 + [i64] * 6 + [vp]),
-    "nkb_linear_gelu": (i32, [i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp]),
-    "nkb_linear_gelu_fused_ok": (i32, [i32, i32, i32, i32]),
-    "nkb_linear_residual_scaled": (i32, [i32, vp, vp, vp, vp, vp, i32, vp, i32, i32, i32, vp]),
-    "nkb_layernorm": (i32, [i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, f32, vp, vp, vp, i32, vp, i32, vp, vp]),
-    "nkb_layernorm_workspace_floats": (sz, [i32]),
-    "nkb_layernorm_param_reduce": (i32, [vp, i32, i32, i32, vp, vp, vp, vp]),
-    "nkb_gelu": (i32, [i32, vp, vp, vp, i64, vp]),
-    "nkb_splitk_reduce": (i32, [i32, vp, i32, i32, i32, vp, i32, vp, vp, vp]),
-    "nkb_wfold": (i32, [i32, vp, vp, vp, i32, i32, vp]),
-    "nkb_image_prep": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, f32, vp]),
-    "nkb_relu6": (i32, [i32, vp, vp, vp, i64, vp]),
-    "nkb_gelu_fwd_dgelu": (i32, [i32, vp, vp, vp, i64, vp]),
-    "nkb_scale_rows": (i32, [i32, vp, vp, vp, vp, i32, i64, vp]),
-    "nkb_attn_softmax": (i32, [i32, i32, vp, i32, vp, vp, i32, i64, i32, f32, vp]),
-    "nkb_attn_forward": (i32, [i32, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp]),
-    "nkb_attn_backward_ds": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, i64, vp]),
-    "nkb_attn_backward": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp]),
-    "nkb_head_transpose": (i32, [i32, vp, i32, i64, i64, i32, i32, vp, i32, i32, i32, vp]),
-    "nkb_vit_assemble": (i32, [i32, i32, vp, vp, vp, vp, i32, i32, i32, vp]),
-    "nkb_dropout": (i32, [i32, i32, vp, vp, vp, vp, i64, f32, C.c_ulonglong, vp]),
-    "nkb_colsum2d": (i32, [i32, vp, vp, i64, i32, i64, vp, vp]),
-    "nkb_loss_forward": (i32, [i32, vp, i32, vp, i32, i32, vp, f32, i64, vp, i32, vp, vp, vp, i32, vp]),
-    "nkb_loss_row_state_bytes": (sz, [i32]),
-    "nkb_loss_backward": (i32, [vp, i32, vp, vp, vp, vp, i32, i32, i32, vp, i32, vp]),
-    "nkb_optim_step": (i32, [i32, vp, vp, vp, vp, vp, i64] + [f32] * 10 + [vp, vp]),
-    "nkb_grad_unscale_check": (i32, [vp, i64, vp, vp, vp]),
-    "nkb_scaler_update": (i32, [vp, vp, vp, vp, f32, f32, i32, vp]),
-    "nkb_bucket_sum_bf16": (i32, [vp, i64, i32, vp, vp, i64, vp]),
-    "nkb_segment_sumsq": (i32, [vp, vp, i32, vp, vp]),
-    "nkb_gemm8p_config": (None, [i32, i32, i32]),
-    "nkb_gemm8p_ragged": (None, [i32]),
-    "nkb_fp8_quantize": (i32, [i32, i32, vp, i64, vp, vp, vp]),
-    "nkb_fp8_amax": (i32, [i32, vp, i64, vp, vp]),
-    "nkb_fp8_scale_update": (i32, [vp, i32, vp]),
-    "nkb_fp8_job_blocks": (i64, [i64]),
-    "nkb_fp8_multi": (i32, [i32, vp, i32, i64, vp]),
-    "nkb_fp8_quantize_colsum_workspace_floats": (i64, [i64, i32]),
-    "nkb_fp8_quantize_colsum": (i32, [i32, vp, i64, i32, i64, vp, vp, vp, vp, vp, i32, vp]),
-    "nkb_wgrad_fp8_workspace_floats": (i64, [i32, i32, i32]),
-    "nkb_wgrad_fp8": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, i64, vp]),
-    "nkb_gemm_fp8": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp] + [i32] * 8 + [vp]),
-    "nkb_dwconv": (i32, [i32, i32, vp, vp, vp, vp, vp] + [i32] * 8 + [vp]),
-    "nkb_dwconv_wgrad": (i32, [i32, vp, vp, vp, vp] + [i32] * 8 + [vp, i64, vp]),
-    "nkb_dwconv_wgrad_workspace_floats": (i64, [i32] * 6),
-    "nkb_layer_scale": (i32, [i32, i32, vp, vp, vp, vp, vp, i64, i32, vp, i64, vp]),
-    "nkb_layer_scale_workspace_floats": (i64, [i64, i32]),
-    "nkb_stem3_tiles": (i32, [i32] * 6),
-    "nkb_stem3_conv": (i32, [i32, i32, vp, vp, vp, vp, vp] + [i32] * 10 + [vp]),
-    "nkb_avgpool2x2": (i32, [i32, i32, vp, vp, i32, i32, i32, i32, vp]),
-    "nkb_prof_enable": (None, [i32]),
-    "nkb_prof_collect": (i32, [vp, vp, vp, vp, i32]),
-    "nkb_prof_collect_raw": (i32, [vp, vp, vp, vp, i32]),
-    "nkb_kernel_name": (C.c_char_p, [i32]),
-    "nkb_plan_fn_count": (i32, []),
-    "nkb_plan_fn_name": (C.c_char_p, [i32]),
-    "nkb_plan_fn_args": (i32, [i32]),
-    "nkb_plan_max_args": (i32, []),
-    "nkb_plan_entry_bytes": (sz, []),
-    "nkb_plan_run": (i32, [vp, i32, vp]),
-}
+# The binding is read off include/nkbhip.h, the header the kernel sources are compiled against (cabi.py).
+_HEADER = cabi.header_text()
+_PROTOS = cabi.parse(_HEADER)
+_SIGS = {name: (p.restype, p.argtypes) for name, p in _PROTOS.items()}      # {entry point: (ctypes restype, [ctypes argtypes])}
 
 
 def lib_path() -> Path:
@@ -185,17 +64,8 @@ def exported_symbols():
 # (input images, logits, logits gradient) and dropout seeds.
 _REC = None            # list of plan entries while recording
 _REC_LIB = None
-_PURE = frozenset({"nkb_kernel_launches", "nkb_linear_gelu_fused_ok", "nkb_version", "nkb_last_error", "nkb_conv_gemm_stat_tiles", "nkb_convp_tiles", "nkb_conv1p_tiles", "nkb_stemp_tiles", "nkb_stemp_wgrad_workspace_floats", "nkb_gramr_workspace_floats", "nkb_bn_stats_floats",
-                   "nkb_bn_backward_workspace_floats", "nkb_wprep_block_elems", "nkb_wprep_job_blocks", "nkb_stem_weight_cols",
-                   "nkb_bn_relu_maxpool_workspace_floats", "nkb_layernorm_workspace_floats", "nkb_loss_row_state_bytes",
-                   "nkb_conv_wgrad_workspace_floats", "nkb_stem_wgrad_workspace_floats", "nkb_kernel_name",
-                   "nkb_prof_enable", "nkb_prof_collect", "nkb_prof_collect_raw", "nkb_gemm8p_config", "nkb_gemm8p_ragged", "nkb_convp_config", "nkb_rowres_reserve_cus", "nkb_rowres_reserved_cus",
-                   "nkb_fp8_job_blocks", "nkb_wgrad_fp8_workspace_floats", "nkb_dwconv_wgrad_workspace_floats",
-                   "nkb_layer_scale_workspace_floats", "nkb_stem3_tiles",
-                   "nkb_fp8_quantize_colsum_workspace_floats",
-                   "nkb_gram_bn_backward_workspace_floats", "nkb_bn_apply_gram_workspace_floats",
-                   "nkb_plan_fn_count", "nkb_plan_fn_name", "nkb_plan_fn_args", "nkb_plan_max_args", "nkb_plan_entry_bytes",
-                   "nkb_plan_run"})
+# entry points that enqueue nothing (declared without a stream parameter): queries and switches, called but never recorded
+_PURE = frozenset(name for name, p in _PROTOS.items() if cabi.STREAM not in p.params)
 
 
 class Seed(int):
@@ -332,7 +202,7 @@ def record_end(dynamic: dict) -> Plan:
                         break
         if name in ids and len(args) <= _PLAN_MAX_ARGS:
             types = _SIGS[name][1]
-            vals = [("f" if t is f32 else ("p" if t is vp else "i"), (0 if a is None and t is not vp else a)) for t, a in zip(types, args)]
+            vals = [("f" if t is C.c_float else ("p" if t is C.c_void_p else "i"), (0 if a is None and t is not C.c_void_p else a)) for t, a in zip(types, args)]
             cur.append((ids[name], vals, name, patches))
         else:
             flush()
@@ -450,14 +320,14 @@ def _device_allocs() -> int:
     return int(torch.cuda.memory_stats(torch.cuda.current_device()).get("allocation.all.allocated", 0))
 
 
+# {"gemm8p": 0, ...}: enum NkbLaunchCounter of the header, NKB_LAUNCH_GEMM8P -> "gemm8p"
+_LAUNCH_COUNTERS = {k[len("NKB_LAUNCH_"):].lower(): v for k, v in cabi.parse_enum(_HEADER, "NkbLaunchCounter").items()}
+
+
 def kernel_launches(which: str, reset: bool = False) -> int:
-    """Launch count of a specialised kernel family: gemm8p, wgrad8p, wgrad3x3, wgrad8f, gram_conv, gram_bn_apply, convp, conv1p, stemp, gramr,
-    wgradr, gemm8p_ragged (the ragged-row companion of a gemm8p launch), gemm_fp8 (the fp8 forms of the gemm8p core), dwconv (depthwise
-    convolution: forward, data and weight gradient), layer_scale, stem3 (narrow 3x3 stem convolution: forward and data gradient), avgpool2
-    (2x2 average pool of the avg_down shortcut: forward and backward)."""
-    idx = {"gemm8p": 0, "wgrad8p": 1, "wgrad3x3": 2, "wgrad8f": 3, "gram_conv": 4, "gram_bn_apply": 5, "convp": 6, "conv1p": 7,
-           "stemp": 8, "gramr": 9, "wgradr": 10, "gemm8p_ragged": 11, "gemm_fp8": 12, "dwconv": 13, "layer_scale": 14, "stem3": 15,
-           "avgpool2": 16}[which]
+    """Launch count of a specialised kernel family; `which` is an enumerator of NkbLaunchCounter (include/nkbhip.h, one comment per
+    family) without its NKB_LAUNCH_ prefix, in lower case: "gemm8p", "convp", "stem3", ..."""
+    idx = _LAUNCH_COUNTERS[which]
     return int(load().nkb_kernel_launches(idx, int(reset)))
 
 

@@ -1,17 +1,169 @@
 """The C-ABI shared library loads (no GPU needed) and exports exactly the symbols include/nkbhip.h declares."""
 import ctypes
 import re
+import shutil
+import subprocess
 from pathlib import Path
 
-from nkb_classification import hip
+import pytest
+
+from nkb_classification import cabi, hip
 
 ROOT = Path(__file__).resolve().parents[1]
+vp, i32, i64, f32, sz, u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_float, ctypes.c_size_t, ctypes.c_ulonglong
 
 
 def _declared():
     text = (ROOT / "include" / "nkbhip.h").read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     return sorted(set(re.findall(r"\b(nkb_[a-z0-9_]+)\s*\(", text)))
+
+
+def _same(row, restype, argtypes):
+    """A signature row equals the literal one class by class (`is`: hip.record_end sorts arguments by class identity)."""
+    return row[0] is restype and len(row[1]) == len(argtypes) and all(a is b for a, b in zip(row[1], argtypes))
+
+
+# ---- the header parser, on literal declarations (independent of the real header) ------------------------------------------
+_DECLS = """
+/* a block comment with a prototype inside: int nkb_ghost(int a); */
+#ifndef X_H
+#define X_H
+#define NKB_TWO_LINES(a) \\
+    int nkb_macro_body(a);
+#ifdef __cplusplus
+extern "C" {
+#endif
+typedef struct ihipStream_t* nkb_stream_t; /* hipStream_t */
+typedef union { void* p; long long i; float f; } Arg;
+typedef struct { int fn; int nargs; Arg a[32]; } Entry;
+struct Opaque;
+enum Counter { COUNTER_A = 0, /* first */ COUNTER_B = 1, COUNTER_C, COUNTER_TEN = 0x0a, COUNTER_ELEVEN };
+int nkb_three_lines(int dtype, const void* x,   /* the input */
+                    // a line comment between parameters: float* ghost,
+                    float* y, long long rows,
+                    nkb_stream_t stream);
+int nkb_no_args(void);
+const char* nkb_text(void);
+void nkb_nothing(int on);
+size_t nkb_by_value(unsigned long long seed, size_t bytes, long long n, float p);
+long long nkb_pointers(const unsigned char* bits, int* out, double* ms, const long long* jobs, unsigned char *mask, int);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_parser_on_literal_declarations():
+    protos = cabi.parse(_DECLS)
+    assert list(protos) == ["nkb_three_lines", "nkb_no_args", "nkb_text", "nkb_nothing", "nkb_by_value", "nkb_pointers"]
+    p = protos["nkb_three_lines"]
+    assert _same(p[:2], i32, [i32, vp, vp, i64, vp])
+    assert (p.ret, p.params) == ("int", ["int", "const void*", "float*", "long long", "nkb_stream_t"])
+    assert _same(protos["nkb_no_args"][:2], i32, []) and protos["nkb_no_args"].params == []
+    assert _same(protos["nkb_text"][:2], ctypes.c_char_p, [])
+    assert _same(protos["nkb_nothing"][:2], None, [i32]) and protos["nkb_nothing"].ret == "void"
+    p = protos["nkb_by_value"]
+    assert _same(p[:2], sz, [u64, sz, i64, f32]) and p.params == ["unsigned long long", "size_t", "long long", "float"]
+    p = protos["nkb_pointers"]
+    assert _same(p[:2], i64, [vp, vp, vp, vp, vp, i32])
+    assert p.params == ["const unsigned char*", "int*", "double*", "const long long*", "unsigned char*", "int"]
+    assert cabi.parse_enum(_DECLS, "Counter") == {"COUNTER_A": 0, "COUNTER_B": 1, "COUNTER_C": 2, "COUNTER_TEN": 10, "COUNTER_ELEVEN": 11}
+    with pytest.raises(ValueError, match="Missing"):
+        cabi.parse_enum(_DECLS, "Missing")
+
+
+@pytest.mark.parametrize("decl", ["int nkb_odd(int a, double x, nkb_stream_t stream);", "int nkb_odd(hipStream_t stream);",
+                                  "int nkb_odd(unsigned n);", "int nkb_odd(float mean[3]);", "double nkb_odd(int a);",
+                                  "float* nkb_odd(int a);", "int nkb_odd(NkbPlanArg a);"])
+def test_parser_refuses_what_it_does_not_know(decl):
+    """A by-value type outside the ABI's vocabulary is an error that names the function, never a guess."""
+    with pytest.raises(ValueError, match="nkb_odd"):
+        cabi.parse("int nkb_fine(int a);\n" + decl)
+
+
+def test_missing_header_is_a_loud_error(monkeypatch, tmp_path):
+    monkeypatch.setattr(cabi, "HEADER", tmp_path / "nkbhip.h")
+    with pytest.raises(RuntimeError, match="nkbhip.h"):
+        cabi.header_text()
+
+
+# ---- the derived binding against literals from the hand-written table it replaced ------------------------------------------
+_PINNED = {
+    "nkb_dropout": (i32, [i32, i32, vp, vp, vp, vp, i64, f32, u64, vp]),
+    "nkb_bn_backward": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, sz, vp]),
+    "nkb_layernorm": (i32, [i32, i32, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, i32, f32, vp, vp, vp, i32, vp, i32, vp, vp]),
+    "nkb_optim_step": (i32, [i32, vp, vp, vp, vp, vp, i64] + [f32] * 10 + [vp, vp]),
+    "nkb_last_error": (ctypes.c_char_p, []),
+    "nkb_convp_config": (None, [i32, i32]),
+    "nkb_bn_stats_floats": (sz, [i32, i32]),
+    "nkb_conv_gemm": (i32, [i32, i32, vp, vp, vp, vp, vp, vp] + [i32] * 18 + [vp, vp]),
+    "nkb_conv1p_tiles": (i32, [i32, i64, i32, i32, i32, i32]),
+    "nkb_image_prep": (i32, [vp, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, f32, vp]),
+    "nkb_gemm_batched": (i32, [i32, vp, vp, vp] + [i32] * 8 + [i64] * 6 + [i32, vp]),
+    "nkb_kernel_launches": (i64, [i32, i32]),
+    "nkb_plan_run": (i32, [vp, i32, vp]),
+}
+
+
+@pytest.mark.parametrize("name", sorted(_PINNED))
+def test_derived_signature_equals_pinned_literal(name):
+    assert len(_PINNED["nkb_layernorm"][1]) == 26
+    assert _same(hip._SIGS[name], *_PINNED[name]), (name, hip._SIGS[name])
+
+
+def test_pure_is_declared_without_a_stream():
+    """hip._PURE (called, never recorded into a launch plan) = the entry points whose prototype has no nkb_stream_t parameter."""
+    for name in ("nkb_stem3_tiles", "nkb_gemm8p_config", "nkb_plan_run", "nkb_kernel_name", "nkb_bn_stats_floats", "nkb_last_error"):
+        assert name in hip._PURE, name
+    for name in ("nkb_stem3_conv", "nkb_bn_apply", "nkb_dropout", "nkb_optim_step", "nkb_fp8_scale_update"):
+        assert name not in hip._PURE, name
+    text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "nkbhip.h").read_text(), flags=re.S)
+    protos = dict(re.findall(r"\b(nkb_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S))
+    assert hip._PURE == frozenset(n for n, params in protos.items() if "nkb_stream_t" not in params)
+    assert isinstance(hip._PURE, frozenset) and len(hip._PURE) == 43 and len(hip._SIGS) == 123
+
+
+_LAUNCH_COUNTERS = {"gemm8p": 0, "wgrad8p": 1, "wgrad3x3": 2, "wgrad8f": 3, "gram_conv": 4, "gram_bn_apply": 5, "convp": 6, "conv1p": 7,
+                    "stemp": 8, "gramr": 9, "wgradr": 10, "gemm8p_ragged": 11, "gemm_fp8": 12, "dwconv": 13, "layer_scale": 14,
+                    "stem3": 15, "avgpool2": 16}
+
+
+def test_launch_counter_names_and_numbers():
+    """The string keys of hip.kernel_launches come from enum NkbLaunchCounter of the header; numbers are part of the ABI."""
+    enum = cabi.parse_enum(cabi.header_text(), "NkbLaunchCounter")
+    assert {k[len("NKB_LAUNCH_"):].lower(): v for k, v in enum.items()} == _LAUNCH_COUNTERS
+    assert all(k.startswith("NKB_LAUNCH_") for k in enum)
+    for name in _LAUNCH_COUNTERS:
+        assert hip.kernel_launches(name) >= 0, name
+    with pytest.raises(KeyError):
+        hip.kernel_launches("no_such_family")
+
+
+def _dynamic_exports():
+    """Defined dynamic symbols of libnkbhip.so (names only), read with nm or ROCm's llvm-readelf; no tool is a failure."""
+    lib = str(hip.lib_path())
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
+    if nm:
+        out = subprocess.run([nm, "-D", "--defined-only", lib], check=True, capture_output=True, text=True).stdout
+        return {line.split()[-1].split("@")[0] for line in out.splitlines() if line.split()}
+    readelf = shutil.which("llvm-readelf") or shutil.which("llvm-readelf", path="/opt/rocm/llvm/bin") or shutil.which("readelf")
+    assert readelf, "neither nm nor llvm-readelf / readelf found: cannot list the exports of libnkbhip.so"
+    out = subprocess.run([readelf, "--dyn-syms", "-W", lib], check=True, capture_output=True, text=True).stdout
+    rows = [line.split() for line in out.splitlines()]
+    return {r[7].split("@")[0] for r in rows if len(r) >= 8 and r[0].rstrip(":").isdigit() and r[6] != "UND"}
+
+
+def test_unmangled_exports_are_exactly_the_header():
+    """Both directions: nothing declared is missing from the library, and no internal helper leaks out as an unmangled nkb_*
+    symbol (an `extern "C"` helper outside the header is an ABI nobody described)."""
+    exported = {s for s in _dynamic_exports() if s.startswith("nkb_")}
+    assert len(exported) >= 100
+    declared = set(cabi.parse(cabi.header_text()))
+    assert exported - declared == set(), f"exported but not declared in include/nkbhip.h: {sorted(exported - declared)}"
+    assert declared - exported == set(), f"declared in include/nkbhip.h but not exported: {sorted(declared - exported)}"
+    assert declared == set(_declared())
 
 
 def test_library_loads_and_exports_header_symbols():
@@ -158,12 +310,13 @@ def test_argument_validation_without_gpu():
 
 
 def test_binding_arity_matches_header():
-    """Every ctypes signature in hip._SIGS has as many arguments as the prototype in include/nkbhip.h (a changed entry point
-    whose binding was not updated would otherwise corrupt the call's argument registers silently)."""
+    """Every ctypes signature in hip._SIGS (derived from include/nkbhip.h by nkb_classification/cabi.py) has as many arguments as
+    this independent regex count of the prototype's parameters: a check of the parser, which splits statements its own way."""
     text = (ROOT / "include" / "nkbhip.h").read_text()
     text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
     protos = dict(re.findall(r"\b(nkb_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S))
     assert len(protos) >= 50
+    assert set(protos) == set(hip._SIGS)
     for name, (_, argtypes) in hip._SIGS.items():
         params = protos[name].strip()
         n = 0 if params in ("", "void") else len([a for a in params.split(",") if a.strip()])
@@ -175,7 +328,6 @@ def test_plan_dispatch_table_is_current_and_validates_entries():
     binding's signature table; the library's table agrees with the binding name by name; a table walk on the host rejects a
     bad function id / argument count before calling anything, validates an entry's geometry through the entry point itself and
     reports the failing index."""
-    import subprocess
     import sys
     assert subprocess.run([sys.executable, str(ROOT / "scripts" / "gen_plan_dispatch.py"), "--check"]).returncode == 0, \
         "plan_dispatch.inc is stale: run python scripts/gen_plan_dispatch.py and rebuild"
