@@ -14,11 +14,17 @@ static inline unsigned grid_for(size_t work_items, int block = 256, unsigned cap
 template <typename T> struct Chunk;
 template <> struct Chunk<bf16_t> {
     static constexpr int N = 8;
+    typedef u32x4 Raw;                                      // a chunk as loaded: kept packed while the load is in flight
+    __device__ static __forceinline__ Raw ldraw(const bf16_t* p) { return *(const u32x4*)p; }
+    __device__ static __forceinline__ void unpack(const Raw& r, float* f) { unpack8(r, f); }
     __device__ static __forceinline__ void load(const bf16_t* p, float* f) { unpack8(*(const u32x4*)p, f); }
     __device__ static __forceinline__ void store(bf16_t* p, const float* f) { *(u32x4*)p = pack8(f); }
 };
 template <> struct Chunk<float> {
     static constexpr int N = 4;
+    typedef f32x4 Raw;
+    __device__ static __forceinline__ Raw ldraw(const float* p) { return *(const f32x4*)p; }
+    __device__ static __forceinline__ void unpack(const Raw& r, float* f) { f[0] = r[0]; f[1] = r[1]; f[2] = r[2]; f[3] = r[3]; }
     __device__ static __forceinline__ void load(const float* p, float* f) {
         const f32x4 v = *(const f32x4*)p;
         f[0] = v[0]; f[1] = v[1]; f[2] = v[2]; f[3] = v[3];
@@ -1129,52 +1135,111 @@ template <> struct SlotWord<4> {
     __device__ __forceinline__ int get(int e) const { return (int)((w >> (8 * e)) & 0xff); }
 };
 
+// Forward.  A thread owns (image, pooled column q, channel chunk) and walks a band of NKB_STEM_BAND pooled rows downwards: per input
+// row it loads the three window columns 2q-1, 2q, 2q+1 (addresses clamped into the image, validity a predicate of the compare, no
+// branch around a load) and keeps that row's winner in column order; a pooled output is the winner of the row winners 2p-1, 2p,
+// 2p+1 in row order, and row 2p+1's winner stays in registers as the first row of output p+1.  Six loads per output, all of them
+// requested before the previous output is finished (one thread per output walking its 3 x 3 window under `continue`s: nine loads
+// that waited for each other).  Selection, per candidate a = rnd(max(c*scale + shift, 0)) — the value bn_apply(relu) would have
+// stored — is maxpool_fwd_kernel's: the first valid tap, replaced by a later one when a > best or a is NaN.  Taken per row and then
+// over the rows this is the row-major scan: a strict > keeps the earliest maximum at both levels, and "a NaN always takes over,
+// only a NaN replaces a NaN" picks the last NaN at both levels.
+// band length: 4 / 7 / 14 / 28 pooled rows measured 153 / 141 / 148 / 163 us on the 256 x 112 x 112 x 64 stem (-DNKB_STEM_BAND=n: A/B builds)
+#ifndef NKB_STEM_BAND
+#define NKB_STEM_BAND 7
+#endif
+template <typename T> struct PoolRow { typename Chunk<T>::Raw v[3]; };
+template <typename T>
+__device__ __forceinline__ void pool_row_load(const T* __restrict__ row, int w0, int w1, int w2, int C, PoolRow<T>& r) {
+    r.v[0] = Chunk<T>::ldraw(row + (size_t)w0 * C);
+    r.v[1] = Chunk<T>::ldraw(row + (size_t)w1 * C);
+    r.v[2] = Chunk<T>::ldraw(row + (size_t)w2 * C);
+}
+// winner of one input row: value a, column slot s (0..2) and the raw input x behind it; ok0 / ok2: columns 2q-1 / 2q+1 are inside
+template <typename T>
+__device__ __forceinline__ void pool_row_winner(const PoolRow<T>& r, bool ok0, bool ok2, const float* sc, const float* sh, float* a,
+                                                float* x, int* s) {
+    constexpr int NC = Chunk<T>::N;
+    float v[3][NC];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Chunk<T>::unpack(r.v[k], v[k]);
+#pragma unroll
+    for (int e = 0; e < NC; ++e) {
+        const float a0 = DT<T>::rnd(fmaxf(v[0][e] * sc[e] + sh[e], 0.f));
+        const float a1 = DT<T>::rnd(fmaxf(v[1][e] * sc[e] + sh[e], 0.f));
+        const float a2 = DT<T>::rnd(fmaxf(v[2][e] * sc[e] + sh[e], 0.f));
+        // selects and unconditional (| and &) predicates, not branches: the choice depends on the data
+        const bool t1 = !ok0 | (a1 > a0) | (a1 != a1);                        // column 2q is always inside
+        const float b1 = t1 ? a1 : a0;
+        const bool t2 = ok2 & ((a2 > b1) | (a2 != a2));
+        a[e] = t2 ? a2 : b1;
+        x[e] = t2 ? v[2][e] : (t1 ? v[1][e] : v[0][e]);
+        s[e] = t2 ? 2 : (int)t1;
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(const T* __restrict__ c, const float* __restrict__ scale,
                                                                   const float* __restrict__ shift, T* __restrict__ y,
                                                                   unsigned char* __restrict__ idx, T* __restrict__ xsel, int N,
                                                                   int H, int W, int C, int P, int Q) {
     constexpr int NC = Chunk<T>::N;
+    constexpr int BAND = NKB_STEM_BAND;
     const unsigned cpr = (unsigned)C / NC;
     const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned cg = t % cpr, pstride = (gridDim.x * blockDim.x) / cpr;
-    const unsigned npix = (unsigned)N * P * Q;
+    const unsigned cg = t % cpr, istride = (gridDim.x * blockDim.x) / cpr;
+    const unsigned nbands = ((unsigned)P + BAND - 1) / BAND;
+    const unsigned nitems = (unsigned)N * nbands * (unsigned)Q;
     float sc[NC], sh[NC];
     ldvec<NC>(scale + cg * NC, sc);
     ldvec<NC>(shift + cg * NC, sh);
-    for (unsigned pix = t / cpr; pix < npix; pix += pstride) {
-        const unsigned q = pix % (unsigned)Q, pn = pix / (unsigned)Q;
-        const unsigned pp = pn % (unsigned)P, n = pn / (unsigned)P;
-        float best[NC], bx[NC];                          // bx: the raw value behind the winner (xsel, for the backward reduction)
-        int bi[NC];
-#pragma unroll
-        for (int e = 0; e < NC; ++e) { best[e] = -INFINITY; bi[e] = 0; bx[e] = 0.f; }
-        bool first = true;
-        for (int r = 0; r < 3; ++r) {
-            const int h = 2 * (int)pp - 1 + r;
-            if ((unsigned)h >= (unsigned)H) continue;
-            for (int s = 0; s < 3; ++s) {
-                const int w = 2 * (int)q - 1 + s;
-                if ((unsigned)w >= (unsigned)W) continue;
-                float v[NC];
-                Chunk<T>::load(c + (((size_t)n * H + h) * W + w) * C + cg * NC, v);
-#pragma unroll
-                for (int e = 0; e < NC; ++e) {
-                    // the value bn_apply(relu) would have stored, then maxpool_fwd_kernel's comparison on it
-                    const float a = DT<T>::rnd(fmaxf(v[e] * sc[e] + sh[e], 0.f));
-                    if (first || a > best[e] || a != a) { best[e] = a; bi[e] = r * 3 + s; bx[e] = v[e]; }
-                }
-                first = false;
+    for (unsigned item = t / cpr; item < nitems; item += istride) {
+        const unsigned q = item % (unsigned)Q, bn = item / (unsigned)Q;
+        const unsigned band = bn % nbands, n = bn / nbands;
+        const int p0 = (int)band * BAND, p1 = p0 + BAND < P ? p0 + BAND : P;
+        const bool ok0 = q > 0, ok2 = 2 * (int)q + 1 < W;
+        const int w1 = 2 * (int)q, w0 = ok0 ? w1 - 1 : w1, w2 = ok2 ? w1 + 1 : w1;
+        const T* img = c + (size_t)n * H * W * C + cg * NC;
+        const size_t rowlen = (size_t)W * C;
+        PoolRow<T> ra, rb, rc;                              // rows 2p-1, 2p, 2p+1 of the output being formed
+        pool_row_load(img + (size_t)(p0 > 0 ? 2 * p0 - 1 : 0) * rowlen, w0, w1, w2, C, ra);
+        pool_row_load(img + (size_t)(2 * p0) * rowlen, w0, w1, w2, C, rb);
+        pool_row_load(img + (size_t)(2 * p0 + 1 < H ? 2 * p0 + 1 : H - 1) * rowlen, w0, w1, w2, C, rc);
+        float ta[NC], tx[NC];                               // winner of row 2p-1 (not used where p == 0)
+        int ts[NC];
+        pool_row_winner<T>(ra, ok0, ok2, sc, sh, ta, tx, ts);
+        for (int p = p0; p < p1; ++p) {
+            PoolRow<T> nb = rb, nc = rc;
+            if (p + 1 < p1) {                               // the next output's rows, requested before this one is finished
+                pool_row_load(img + (size_t)(2 * p + 2) * rowlen, w0, w1, w2, C, nb);     // 2(p+1) <= H-1 for p+1 < P
+                pool_row_load(img + (size_t)(2 * p + 3 < H ? 2 * p + 3 : H - 1) * rowlen, w0, w1, w2, C, nc);
             }
-        }
-        const size_t o = (size_t)pix * C + cg * NC;
-        Chunk<T>::store(y + o, best);
-        if (xsel) Chunk<T>::store(xsel + o, bx);
-        unsigned long long word = 0;
+            float ma[NC], mx[NC], la[NC], lx[NC], best[NC], bx[NC];
+            int ms[NC], ls[NC];
+            pool_row_winner<T>(rb, ok0, ok2, sc, sh, ma, mx, ms);
+            pool_row_winner<T>(rc, ok0, ok2, sc, sh, la, lx, ls);
+            const bool okt = p > 0, okl = 2 * p + 1 < H;    // row 2p is always inside
+            unsigned long long word = 0;
 #pragma unroll
-        for (int e = 0; e < NC; ++e) word |= (unsigned long long)bi[e] << (8 * e);
-        if (NC == 8) *(unsigned long long*)(idx + o) = word;
-        else *(unsigned*)(idx + o) = (unsigned)word;
+            for (int e = 0; e < NC; ++e) {
+                const bool t1 = !okt | (ma[e] > ta[e]) | (ma[e] != ma[e]);
+                const float b1 = t1 ? ma[e] : ta[e];
+                const bool t2 = okl & ((la[e] > b1) | (la[e] != la[e]));
+                best[e] = t2 ? la[e] : b1;
+                bx[e] = t2 ? lx[e] : (t1 ? mx[e] : tx[e]);
+                const int m3 = 3 + ms[e], l6 = 6 + ls[e];
+                const int b1i = t1 ? m3 : ts[e];
+                const int bi = t2 ? l6 : b1i;
+                word |= (unsigned long long)bi << (8 * e);
+                ta[e] = la[e]; tx[e] = lx[e]; ts[e] = ls[e];               // row 2p+1 is row 2(p+1)-1
+            }
+            const size_t o = ((((size_t)n * P + p) * Q + q) * C) + cg * NC;
+            Chunk<T>::store(y + o, best);
+            if (xsel) Chunk<T>::store(xsel + o, bx);
+            if (NC == 8) *(unsigned long long*)(idx + o) = word;
+            else *(unsigned*)(idx + o) = (unsigned)word;
+            rb = nb; rc = nc;
+        }
     }
 }
 
@@ -1247,6 +1312,11 @@ __global__ void bn_relu_maxpool_bwd_reduce_kernel(const T* __restrict__ g, const
 // backward pass 2 (input domain): dc = gamma*invstd*(g' - sum_g/M - xhat*sum_gx/M), g' gathered from the <=4 windows.
 // The grid-stride is a multiple of C/NC, so a thread keeps its channel chunk and the per-channel constants stay in
 // registers (dc = k1*g' + k2*c + k3, as in bn_bwd_apply_kernel).
+// A thread produces the 2 x 2 block of input pixels (rows 2p, 2p+1) x (columns 2q, 2q+1): the block lies in exactly the four
+// windows A = (p, q), B = (p, q+1), C = (p+1, q), D = (p+1, q+1) — an even row or column belongs to one window along its axis, an odd
+// one to two — so four c chunks and four (g, idx) pairs serve four pixels (160 bytes requested per 64 stored; one thread per pixel
+// with four candidate windows each requested 448).  All twelve loads are unconditional (window and pixel indices clamped at the
+// bottom and right edges, contributions and stores gated), and every pixel adds its windows in the order A, B, C, D.
 template <typename T>
 __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_apply_kernel(
     const T* __restrict__ g, const unsigned char* __restrict__ idx, const T* __restrict__ c,
@@ -1256,8 +1326,8 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_apply_kernel(
     constexpr int NC = Chunk<T>::N;
     const unsigned cpr = (unsigned)C / NC;
     const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;
-    const unsigned cg = t % cpr, pstride = (gridDim.x * blockDim.x) / cpr;
-    const unsigned npix = (unsigned)N * H * W;
+    const unsigned cg = t % cpr, bstride = (gridDim.x * blockDim.x) / cpr;
+    const unsigned nblk = (unsigned)N * P * Q;               // P = ceil(H/2), Q = ceil(W/2): one 2 x 2 block per pooled position
     float k1[NC], k2[NC], k3[NC], fs[NC], fb[NC], v_is[NC], v_ga[NC], v_mu[NC], v_s1[NC], v_s2[NC];
     ldvec<NC>(scale + cg * NC, fs);
     ldvec<NC>(shift + cg * NC, fb);
@@ -1275,43 +1345,56 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_bwd_apply_kernel(
         k2[e] = -a * is * sdyx;
         k3[e] = -a * sdy + a * is * sdyx * mu;
     }
-    for (unsigned pix = t / cpr; pix < npix; pix += pstride) {
-        const unsigned w = pix % (unsigned)W, hn = pix / (unsigned)W;
-        const unsigned h = hn % (unsigned)H, n = hn / (unsigned)H;
-        float acc[NC], xv[NC], out[NC];
-        const size_t ofs = (size_t)pix * C + cg * NC;
-        Chunk<T>::load(c + ofs, xv);
-#pragma unroll
-        for (int e = 0; e < NC; ++e) acc[e] = 0.f;
-        // the (up to) 2 x 2 pooled windows this pixel belongs to, as four unconditional candidates: all eight loads are requested
-        // together (addresses clamped, contributions gated) — as two nested loops with data-dependent bounds every pair of loads
-        // waited for the previous one (274 us for the 112 x 112 x 64 stem at batch 256)
-        const int p0 = h >> 1, p1 = (h + 1) >> 1, q0 = w >> 1, q1 = (w + 1) >> 1;
-        float gv[4][NC];
+    for (unsigned blk = t / cpr; blk < nblk; blk += bstride) {
+        const unsigned q = blk % (unsigned)Q, pn = blk / (unsigned)Q;
+        const unsigned p = pn % (unsigned)P, n = pn / (unsigned)P;
+        const int h0 = 2 * (int)p, w0 = 2 * (int)q;
+        const bool row1 = h0 + 1 < H, col1 = w0 + 1 < W;                    // the block's second row / column exists
+        const bool okp = (int)p + 1 < P, okq = (int)q + 1 < Q;             // so do the windows below / to the right
+        // element offsets of the block's pixel (0, 0) and window A, and the steps to the second row / column (0 where clamped)
+        const size_t x0 = ((((size_t)n * H + h0) * W + w0) * C) + cg * NC, g0 = (size_t)blk * C + cg * NC;
+        const unsigned xstep[2] = {col1 ? (unsigned)C : 0u, row1 ? (unsigned)W * C : 0u};
+        const unsigned gstep[2] = {okq ? (unsigned)C : 0u, okp ? (unsigned)Q * C : 0u};
+        typename Chunk<T>::Raw xr[4], gr[4];
         SlotWord<NC> sw[4];
-        int slot[4];
-        bool ok[4];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int pp = (k >> 1) ? p1 : p0, q = (k & 1) ? q1 : q0;
-            ok[k] = pp < P && q < Q && !((k >> 1) && p1 == p0) && !((k & 1) && q1 == q0);
-            const int pc = pp < P ? pp : P - 1, qc = q < Q ? q : Q - 1;
-            slot[k] = ((int)h - (2 * pp - 1)) * 3 + ((int)w - (2 * q - 1));
-            const size_t o = ((((size_t)n * P + pc) * Q + qc) * C) + cg * NC;
-            Chunk<T>::load(g + o, gv[k]);
+        for (int k = 0; k < 4; ++k) {                                       // k = 2 * (row of the block) + column; windows A..D alike
+            xr[k] = Chunk<T>::ldraw(c + x0 + (k & 1) * xstep[0] + (k >> 1) * xstep[1]);
+            const size_t o = g0 + (k & 1) * gstep[0] + (k >> 1) * gstep[1];
+            gr[k] = Chunk<T>::ldraw(g + o);
             sw[k].load(idx + o);
         }
+        __builtin_amdgcn_sched_barrier(0);                                  // all twelve requests leave before the first use
+        const bool okw[4] = {true, okq, okp, okp && okq};
+        float gv[4][NC];
 #pragma unroll
-        for (int k = 0; k < 4; ++k)
+        for (int k = 0; k < 4; ++k) Chunk<T>::unpack(gr[k], gv[k]);
+        // Pixels are stored last to first and without a branch (a branch around a store draws that pixel's loads into it, behind the
+        // other pixels' work).  A pixel outside the image (odd H or W: the block's second row or column) has its address clamped onto
+        // a pixel of the block that comes earlier in k, so what it writes there is overwritten by that pixel's own store from the same
+        // thread further down.
 #pragma unroll
-            for (int e = 0; e < NC; ++e) if (ok[k] && sw[k].get(e) == slot[k]) acc[e] += gv[k][e];
+        for (int k = 3; k >= 0; --k) {
+            const int dh = k >> 1, dw = k & 1;
+            float xv[NC], out[NC];
+            Chunk<T>::unpack(xr[k], xv);
 #pragma unroll
-        for (int e = 0; e < NC; ++e) {
-            float gg = acc[e];
-            if (!(DT<T>::rnd(xv[e] * fs[e] + fb[e]) > 0.f)) gg = 0.f;
-            out[e] = k1[e] * gg + (k2[e] * xv[e] + k3[e]);
+            for (int e = 0; e < NC; ++e) {
+                float gg = 0.f;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    // window j = 2*jp + jq holds pixel (dh, dw) of the block at slot 3*r + s; an even row (column) lies only in
+                    // the block's own window row (column)
+                    const int jp = j >> 1, jq = j & 1;
+                    if ((jp && !dh) || (jq && !dw)) continue;
+                    const int r = dh ? (jp ? 0 : 2) : 1, s = dw ? (jq ? 0 : 2) : 1;
+                    if (okw[j] && sw[j].get(e) == 3 * r + s) gg += gv[j][e];
+                }
+                if (!(DT<T>::rnd(xv[e] * fs[e] + fb[e]) > 0.f)) gg = 0.f;
+                out[e] = k1[e] * gg + (k2[e] * xv[e] + k3[e]);
+            }
+            Chunk<T>::store(dc + x0 + (k & 1) * xstep[0] + (k >> 1) * xstep[1], out);
         }
-        Chunk<T>::store(dc + ofs, out);
     }
 }
 
@@ -1338,7 +1421,10 @@ extern "C" int nkb_bn_relu_maxpool_sel(int dtype, int backward, const void* c, c
     if ((long long)N * H * W >= (1ll << 31)) { nkb_set_error("bn_relu_maxpool: N*H*W too large"); return 1; }
     if (!backward) {
         NkbProfScope prof(NKB_K_MAXPOOL, stream, 0);
-        const unsigned grid = grid_cols((size_t)N * P * Q, C / n);
+        // one thread per (image, band of pooled rows, pooled column, chunk); a band is NKB_STEM_BAND times an output's work, so the
+        // grid is not capped at the streaming kernels' 2048 blocks until the extent is four times the ResNet stem's at batch 256
+        const size_t nbands = (size_t)(P + NKB_STEM_BAND - 1) / NKB_STEM_BAND;
+        const unsigned grid = grid_cols((size_t)N * nbands * Q, C / n, 16384);
         if (dtype == NKB_DT_BF16)
             hipLaunchKernelGGL(bn_relu_maxpool_fwd_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream,
                                (const bf16_t*)c, scale, shift, (bf16_t*)y_or_g, idx, (bf16_t*)xsel, N, H, W, C, P, Q);
@@ -1375,7 +1461,7 @@ extern "C" int nkb_bn_relu_maxpool_sel(int dtype, int backward, const void* c, c
     if (int rc = nkb_check_launch("bn_relu_maxpool_bwd_reduce")) return rc;
     {
         NkbProfScope prof(NKB_K_BN_BWD_APPLY, stream, 0);
-        const unsigned grid = grid_cols((size_t)N * H * W, cpr);
+        const unsigned grid = grid_cols((size_t)N * P * Q, cpr);          // one thread per (2 x 2 pixel block, chunk)
         const float inv_count = 1.0f / (float)((long long)N * H * W);
         if (dtype == NKB_DT_BF16)
             hipLaunchKernelGGL(bn_relu_maxpool_bwd_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream,
@@ -1401,21 +1487,33 @@ extern "C" size_t nkb_bn_relu_maxpool_workspace_floats(int N, int H, int W, int 
 // Packed stem helpers (see nkb_stem_conv in conv_igemm.hip for the layout).
 // pack: NCHW fp32 image -> [N][H][Wp][4] in the compute dtype (Wp = W rounded up to even), channels >= C and the
 // extra column zero (a zero column on the right is what the convolution's own padding would have supplied).
+// A thread packs two neighbouring pixels (Wp is even, so a pair never straddles a row) and stores 16 bytes in bf16; with an even W
+// the two source columns of a channel are one aligned 8-byte load.
 template <typename T>
 __global__ void stem_pack_kernel(const float* __restrict__ x, T* __restrict__ out, int N, int C, int H, int W, int Wp) {
-    const size_t total = (size_t)N * H * Wp;
+    const int Wh = Wp / 2;
+    const size_t total = (size_t)N * H * Wh;
+    const bool even = (W & 1) == 0;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int w = (int)(i % Wp);
-        const size_t nh = i / Wp;
+        const int w = 2 * (int)(i % Wh);                 // w < W; w + 1 may be the added zero column
+        const size_t nh = i / Wh;
         const size_t n = nh / H, h = nh - n * H;
-        float v[4] = {0.f, 0.f, 0.f, 0.f};
-        if (w < W)
-            for (int c = 0; c < C; ++c) v[c] = x[((n * C + c) * H + h) * W + w];
+        float v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < C; ++c) {
+            const float* src = x + ((n * C + c) * H + h) * W + w;
+            if (even) {
+                const nkb_f2 two = *(const nkb_f2*)src;
+                v[c] = two[0]; v[4 + c] = two[1];
+            } else {
+                v[c] = src[0];
+                if (w + 1 < W) v[4 + c] = src[1];
+            }
+        }
         if constexpr (sizeof(T) == 2) {
-            u32x2 o = {pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3])};
-            *(u32x2*)(out + i * 4) = o;
+            *(u32x4*)(out + i * 8) = pack8(v);
         } else {
-            *(f32x4*)(out + i * 4) = (f32x4){v[0], v[1], v[2], v[3]};
+            *(f32x4*)(out + i * 8) = (f32x4){v[0], v[1], v[2], v[3]};
+            *(f32x4*)(out + i * 8 + 4) = (f32x4){v[4], v[5], v[6], v[7]};
         }
     }
 }
@@ -1423,7 +1521,7 @@ extern "C" int nkb_stem_pack(int dtype, const float* x, void* out, int N, int C,
     if (C < 1 || C > 4) { nkb_set_error("stem_pack: C=%d outside 1..4", C); return 1; }
     NkbProfScope prof(NKB_K_IM2COL, stream, 0);
     const int Wp = (W + 1) & ~1;
-    const size_t total = (size_t)N * H * Wp;
+    const size_t total = (size_t)N * H * (Wp / 2);
     if (dtype == NKB_DT_BF16) hipLaunchKernelGGL(stem_pack_kernel<bf16_t>, dim3(grid_for(total)), dim3(256), 0, stream, x, (bf16_t*)out, N, C, H, W, Wp);
     else hipLaunchKernelGGL(stem_pack_kernel<float>, dim3(grid_for(total)), dim3(256), 0, stream, x, (float*)out, N, C, H, W, Wp);
     return nkb_check_launch("stem_pack");
