@@ -333,6 +333,9 @@ int nkb_linear_residual_scaled(int dtype, const void* x, const void* w, const fl
 /* LayerNorm over the last dim (biased variance). backward=0: in = x -> out = y, writes mean/rstd.
  * backward=1: in = dy, x = saved input -> out = dx (+ add), dgamma/dbeta accumulated (workspace: per-block partials added in a
  * fixed order; NULL: atomics). Strides in elements.
+ * D % 8 == 0, 8 <= D <= 2048.  D % 128 == 0 (up to 2048 when D % 256 == 0, else up to 1024) runs the full-lane kernels: strides
+ * multiples of 4 resp. 2 elements.  Every other width runs their masked-tail form (four-element vectors, ceil(D / 256) passes, the
+ * lanes beyond D neither load nor store): strides multiples of 4 elements.  Refusals name D= or the strides.
  * yq / q_state / q_kind (optional, D % 256 == 0, out_stride == D): fp8 copy of the output rows for the fp8 GEMM that consumes
  * them (see nkb_fp8_quantize).  Backward (workspace form only): the copy is of row_scale[row / rows_per_sample] * dx (row_scale
  * optional: the stochastic-depth factor of the branch the gradient enters) and colsum[D] += its column sums — the operand and
@@ -348,7 +351,8 @@ int nkb_layernorm(int dtype, int backward, const void* in, long long in_stride, 
 size_t nkb_layernorm_workspace_floats(int D); /* backward: optional scratch for the deterministic dgamma/dbeta reduction */
 /* Workspace-form backward with dgamma = dbeta = NULL leaves only the per-block partial rows in `workspace`; this call then adds their
  * ordered sums to dgamma / dbeta (and colsum when planes == 3: the launch wrote an fp8 copy) — on any stream ordered after that
- * launch, so that the two small reduction launches need not sit in the backward chain.  rows, D as in that launch. */
+ * launch, so that the two small reduction launches need not sit in the backward chain.  rows, D as in that launch (any D
+ * nkb_layernorm takes). */
 int nkb_layernorm_param_reduce(float* workspace, int rows, int D, int planes, float* dgamma, float* dbeta, float* colsum,
                                nkb_stream_t stream);
 /* exact-erf GELU: dy == NULL -> out = gelu(x); else out = dy * gelu'(x) */

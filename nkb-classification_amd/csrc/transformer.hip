@@ -356,6 +356,147 @@ __global__ __launch_bounds__(256, 8) void layernorm_bwd_lean_kernel(const bf16_t
     }
 }
 
+// Masked-tail form of the two register kernels above, for the widths they are not compiled for: any D % 8 == 0 up to 2048 (ViT-Tiny's
+// 192, the ConvNeXt stage widths 96 ... 1536).  VW = 4 and NP = ceil(D / 256) passes; the passes before the last are full, the last
+// has D / 4 - 64 (NP - 1) active lanes.  An inactive lane neither loads nor stores and holds exact zeros where the wave sums read it;
+// mean and variance divide by the true D.  One row per wave at every width (a row of D <= 128 leaves half the lanes idle: no
+// two-rows-per-wave layout here).  No second outputs.
+template <typename T, int NP>
+__global__ __launch_bounds__(256) void layernorm_fwd_tail_kernel(const T* __restrict__ x, long long xs, const float* __restrict__ gamma,
+                                                                 const float* __restrict__ beta, T* __restrict__ y, long long ys,
+                                                                 float* __restrict__ mean, float* __restrict__ rstd, int rows, int D,
+                                                                 float eps) {
+    constexpr int VW = 4;
+    const int lane = threadIdx.x & 63;
+    const int wpb = blockDim.x >> 6;
+    const bool last = ((NP - 1) * 64 + lane) * VW < D;      // this lane holds a vector of the last pass
+    for (int row = blockIdx.x * wpb + (threadIdx.x >> 6); row < rows; row += gridDim.x * wpb) {
+        const T* xr = x + (size_t)row * xs;
+        float v[NP][VW];
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            if (k < NP - 1 || last) VecIO<T, VW>::ld(xr + (k * 64 + lane) * VW, v[k]);
+            else {
+#pragma unroll
+                for (int e = 0; e < VW; ++e) v[k][e] = 0.f;
+            }
+#pragma unroll
+            for (int e = 0; e < VW; ++e) s += v[k][e];
+        }
+        const float mu = wave_sum(s) / (float)D;
+        float q = 0.f;
+#pragma unroll
+        for (int k = 0; k < NP; ++k)
+            if (k < NP - 1 || last) {
+#pragma unroll
+                for (int e = 0; e < VW; ++e) { const float a = v[k][e] - mu; q += a * a; }
+            }
+        const float rs = 1.0f / sqrtf(wave_sum(q) / (float)D + eps);
+        T* yr = y + (size_t)row * ys;
+#pragma unroll
+        for (int k = 0; k < NP; ++k)
+            if (k < NP - 1 || last) {
+                const int e0 = (k * 64 + lane) * VW;
+                float o[VW];
+#pragma unroll
+                for (int e = 0; e < VW; ++e) o[e] = (v[k][e] - mu) * rs * gamma[e0 + e] + beta[e0 + e];
+                VecIO<T, VW>::st(yr + e0, o);
+            }
+        if (lane == 0 && mean) { mean[row] = mu; rstd[row] = rs; }
+    }
+}
+
+template <typename T, int NP>
+__global__ __launch_bounds__(256, NP <= 4 ? NKB_LN_BWD_OCC : 1) void layernorm_bwd_tail_kernel(const T* __restrict__ dy, long long dys, const T* __restrict__ x,
+                                                            long long xs, const float* __restrict__ mean,
+                                                            const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                            const T* __restrict__ add, T* __restrict__ dx, long long dxs,
+                                                            float* __restrict__ dgamma, float* __restrict__ dbeta, int rows, int D,
+                                                            float* __restrict__ part) {
+    constexpr int VW = 4;
+    __shared__ float red[4][2][64 * VW];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int wpb = blockDim.x >> 6;
+    const bool last = ((NP - 1) * 64 + lane) * VW < D;
+    float ag[NP][VW], ab[NP][VW], gam[NP][VW];
+#pragma unroll
+    for (int k = 0; k < NP; ++k)
+#pragma unroll
+        for (int e = 0; e < VW; ++e) { ag[k][e] = 0.f; ab[k][e] = 0.f; gam[k][e] = (k < NP - 1 || last) ? gamma[(k * 64 + lane) * VW + e] : 0.f; }
+    for (int row = blockIdx.x * wpb + wave; row < rows; row += gridDim.x * wpb) {
+        const T* xr = x + (size_t)row * xs;
+        const T* gr = dy + (size_t)row * dys;
+        const float mu = mean[row], rs = rstd[row];
+        float xh[NP][VW], g[NP][VW];
+        float c1 = 0.f, c2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {
+            if (k < NP - 1 || last) {
+                VecIO<T, VW>::ld(xr + (k * 64 + lane) * VW, xh[k]);
+                VecIO<T, VW>::ld(gr + (k * 64 + lane) * VW, g[k]);
+#pragma unroll
+                for (int e = 0; e < VW; ++e) {
+                    xh[k][e] = (xh[k][e] - mu) * rs;
+                    ag[k][e] += g[k][e] * xh[k][e];
+                    ab[k][e] += g[k][e];
+                    g[k][e] *= gam[k][e];
+                    c1 += g[k][e];
+                    c2 += g[k][e] * xh[k][e];
+                }
+            } else {
+#pragma unroll
+                for (int e = 0; e < VW; ++e) { xh[k][e] = 0.f; g[k][e] = 0.f; }
+            }
+        }
+        typename VecIO<T, VW>::Raw araw[NP];
+        if (add) {
+#pragma unroll
+            for (int k = 0; k < NP; ++k)
+                if (k < NP - 1 || last) araw[k] = VecIO<T, VW>::ldr(add + (size_t)row * dxs + (k * 64 + lane) * VW);
+        }
+        c1 = wave_sum(c1) / (float)D;
+        c2 = wave_sum(c2) / (float)D;
+        T* or_ = dx + (size_t)row * dxs;
+#pragma unroll
+        for (int k = 0; k < NP; ++k)
+            if (k < NP - 1 || last) {
+                const int e0 = (k * 64 + lane) * VW;
+                float o[VW], a[VW];
+                if (add) VecIO<T, VW>::cvt(araw[k], a);
+#pragma unroll
+                for (int e = 0; e < VW; ++e) {
+                    o[e] = rs * (g[k][e] - c1 - xh[k][e] * c2);
+                    if (add) o[e] += a[e];
+                }
+                VecIO<T, VW>::st(or_ + e0, o);
+            }
+    }
+    // block reduction of the per-lane column sums (columns beyond D: nothing to write), as in the register form
+#pragma unroll
+    for (int k = 0; k < NP; ++k) {
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < VW; ++e) { red[wave][0][lane * VW + e] = ag[k][e]; red[wave][1][lane * VW + e] = ab[k][e]; }
+        __syncthreads();
+        if (wave == 0 && (k < NP - 1 || last)) {
+#pragma unroll
+            for (int e = 0; e < VW; ++e) {
+                float s0 = 0.f, t0 = 0.f;
+                for (int w = 0; w < wpb; ++w) { s0 += red[w][0][lane * VW + e]; t0 += red[w][1][lane * VW + e]; }
+                const int col = (k * 64 + lane) * VW + e;
+                if (part) {
+                    part[((size_t)blockIdx.x * 2) * D + col] = s0;
+                    part[((size_t)blockIdx.x * 2 + 1) * D + col] = t0;
+                } else {
+                    atomicAdd(dgamma + col, s0);
+                    atomicAdd(dbeta + col, t0);
+                }
+            }
+        }
+    }
+}
+
 // Second stage of the deterministic LayerNorm parameter gradients, itself in two launches: with one block per 64 columns (16 blocks
 // for D = 1024) the 1024 partial rows were read by 16 CUs and the launch took 21 us — longer than a third of the backward kernel
 // it follows.  Now LN_SLICES blocks per column group each sum a contiguous slice of the partial rows (fixed order), and a tiny
@@ -447,6 +588,24 @@ static int ln_dispatch(int np, int backward, int grid, hipStream_t stream, const
     return 1;
 }
 
+// the masked-tail form: np = ceil(D / 256) passes of four-element vectors
+template <typename T>
+static int ln_tail_dispatch(int np, int backward, int grid, hipStream_t stream, const void* in, long long is, const void* x, long long xs,
+                            const float* g, const float* b, float* mean, float* rstd, const void* add, void* out, long long os,
+                            float* dg, float* db, int rows, int D, float eps, float* part) {
+#define LN_CASE(N) case N: \
+        if (!backward) hipLaunchKernelGGL((layernorm_fwd_tail_kernel<T, N>), dim3(grid), dim3(256), 0, stream, (const T*)in, is, g, b, (T*)out, os, mean, rstd, rows, D, eps); \
+        else hipLaunchKernelGGL((layernorm_bwd_tail_kernel<T, N>), dim3(grid), dim3(256), 0, stream, (const T*)in, is, (const T*)x, xs, mean, rstd, g, (const T*)add, (T*)out, os, dg, db, rows, D, part); \
+        return 0;
+    switch (np) { LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(7) LN_CASE(8) }
+#undef LN_CASE
+    return 1;
+}
+
+// D % 128 == 0 within the full-lane instantiations (VW 4 up to 2048, VW 2 up to 1024): those kernels, unchanged; every other width
+// takes the masked-tail form
+static bool ln_full_lanes(int D) { return D % 128 == 0 && D >= 128 && D <= (D % 256 == 0 ? 2048 : 1024); }
+
 extern "C" size_t nkb_layernorm_workspace_floats(int D) { return (size_t)2048 * 2 * D; }
 
 // partial rows (= workgroups) of a workspace-form backward launch over `rows` rows
@@ -476,8 +635,8 @@ static void ln_param_reduce(float* workspace, int grid, int D, int planes, float
 // can put these two small launches on another stream than the backward chain (they only feed parameter gradients).
 extern "C" int nkb_layernorm_param_reduce(float* workspace, int rows, int D, int planes, float* dgamma, float* dbeta, float* colsum,
                                           hipStream_t stream) {
-    if (!workspace || !dgamma || !dbeta || (planes != 2 && planes != 3) || (planes == 3 && !colsum) || D % 128 != 0 || rows < 1) {
-        nkb_set_error("layernorm_param_reduce: bad arguments (planes %d, D %d, rows %d)", planes, D, rows);
+    if (!workspace || !dgamma || !dbeta || (planes != 2 && planes != 3) || (planes == 3 && !colsum) || D % 8 != 0 || D < 8 || D > 2048 || rows < 1) {
+        nkb_set_error("layernorm_param_reduce: bad arguments (planes %d, D=%d must be a multiple of 8 in [8, 2048], rows %d)", planes, D, rows);
         return 1;
     }
     NkbProfScope prof(NKB_K_LN, stream, 0);
@@ -494,18 +653,24 @@ extern "C" int nkb_layernorm(int dtype, int backward, const void* in, long long 
                              long long out_stride, float* dgamma, float* dbeta, int rows, int D, float eps,
                              float* workspace, void* yq, float* q_state, int q_kind, const float* row_scale, int rows_per_sample,
                              float* colsum, hipStream_t stream) {
-    const int vw = (D % 256 == 0) ? 4 : 2;
-    const int np = D / (64 * vw);
-    if (D % 128 != 0 || np < 1 || np > 8 || in_stride % vw || x_stride % vw || out_stride % vw) {
-        nkb_set_error("layernorm: D=%d must be a multiple of 128 (<= 2048) with vector-aligned strides", D);
+    if (D % 8 != 0 || D < 8 || D > 2048) {
+        nkb_set_error("layernorm: D=%d must be a multiple of 8 in [8, 2048]", D);
+        return 1;
+    }
+    const bool tail = !ln_full_lanes(D);                     // masked-tail form: four-element vectors, ceil(D / 256) passes
+    const int vw = (tail || D % 256 == 0) ? 4 : 2;
+    const int np = tail ? (D + 255) / 256 : D / (64 * vw);
+    if (in_stride % vw || x_stride % vw || out_stride % vw) {
+        nkb_set_error("layernorm: in_stride=%lld, x_stride=%lld and out_stride=%lld must be multiples of %d elements at D=%d", in_stride,
+                      x_stride, out_stride, vw, D);
         return 1;
     }
     const bool scaled_copy = yq && q_kind == 2;              // backward only: yq = row_scale * dx in the compute dtype (bf16)
-    if (scaled_copy && (!backward || dtype != NKB_DT_BF16 || vw != 4 || out_stride != D || !row_scale || rows_per_sample < 1 || q_state || colsum)) {
+    if (scaled_copy && (!backward || dtype != NKB_DT_BF16 || D % 256 != 0 || out_stride != D || !row_scale || rows_per_sample < 1 || q_state || colsum)) {
         nkb_set_error("layernorm: the scaled copy (q_kind 2) goes with backward, bf16, D %% 256 == 0, packed rows, row_scale and nothing else");
         return 1;
     }
-    if (yq && !scaled_copy && (dtype != NKB_DT_BF16 || vw != 4 || out_stride != D || !q_state || (q_kind != 0 && q_kind != 1))) {
+    if (yq && !scaled_copy && (dtype != NKB_DT_BF16 || D % 256 != 0 || out_stride != D || !q_state || (q_kind != 0 && q_kind != 1))) {
         nkb_set_error("layernorm: the fp8 output needs bf16 rows, D %% 256 == 0, packed rows and a scaling state");
         return 1;
     }
@@ -522,7 +687,10 @@ extern "C" int nkb_layernorm(int dtype, int backward, const void* in, long long 
     else if (workspace) grid = ln_bwd_blocks(rows);           // partials [grid][2 or 3][D] in the workspace
     else if (grid > 512) grid = 512;                         // atomics path: keep same-address contention low
     int rc;
-    if (dtype == NKB_DT_BF16)
+    if (tail)
+        rc = dtype == NKB_DT_BF16 ? ln_tail_dispatch<bf16_t>(np, backward, grid, stream, in, in_stride, x, x_stride, gamma, beta, mean, rstd, add, out, out_stride, dgamma, dbeta, rows, D, eps, workspace)
+                                  : ln_tail_dispatch<float>(np, backward, grid, stream, in, in_stride, x, x_stride, gamma, beta, mean, rstd, add, out, out_stride, dgamma, dbeta, rows, D, eps, workspace);
+    else if (dtype == NKB_DT_BF16)
         rc = vw == 4 ? ln_dispatch<bf16_t, 4>(np, backward, grid, stream, in, in_stride, x, x_stride, gamma, beta, mean, rstd, add, out, out_stride, dgamma, dbeta, rows, eps, workspace, (unsigned char*)yq, q_state, q_kind, row_scale, rows_per_sample)
                      : ln_dispatch<bf16_t, 2>(np, backward, grid, stream, in, in_stride, x, x_stride, gamma, beta, mean, rstd, add, out, out_stride, dgamma, dbeta, rows, eps, workspace, (unsigned char*)yq, q_state, q_kind, row_scale, rows_per_sample);
     else

@@ -342,12 +342,12 @@ def create_backbone(name: str, pretrained: bool = False) -> nn.Module:
     if key in _RESNETS:
         blk, layers, *extra = _RESNETS[key]
         return HipResNet(blk, layers, **(extra[0] if extra else {}))
-    from .vit import create_vit
+    from .vit import create_vit, vit_members
     m = create_vit(key)
     if m is None:
         from .convnext import _CONVNEXTS, create_convnext
         m = create_convnext(key)
     if m is None:
         raise NotImplementedError(f"backbone {name!r} is not implemented by the HIP engine "
-                                  f"(available: {sorted(_RESNETS)} + vit_{{small,base,large}}_patch16_224 + {sorted(_CONVNEXTS)})")
+                                  f"(available: {sorted(_RESNETS)} + {vit_members()} + {sorted(_CONVNEXTS)})")
     return m

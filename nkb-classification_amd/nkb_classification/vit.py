@@ -201,11 +201,32 @@ _VITS = {
     "vit_base_patch16_224": dict(img=224, patch=16, dim=768, depth=12, heads=12),
     "vit_small_patch16_224": dict(img=224, patch=16, dim=384, depth=12, heads=6),
     "vit_large_patch16_224": dict(img=224, patch=16, dim=1024, depth=24, heads=16),
+    # dim 192 (three heads of 64): LayerNorm rows on the masked-tail kernels, no GEMM inside the gemm8p envelope, no fp8
+    "vit_tiny_patch16_224": dict(img=224, patch=16, dim=192, depth=12, heads=3),
+    "vit_tiny_patch16_384": dict(img=384, patch=16, dim=192, depth=12, heads=3),
+    # patch 32 (T = 50) and 384 px (T = 577: the unfused attention path, as unicom ViT-L/14@336px)
+    "vit_small_patch32_224": dict(img=224, patch=32, dim=384, depth=12, heads=6),
+    "vit_small_patch16_384": dict(img=384, patch=16, dim=384, depth=12, heads=6),
+    "vit_base_patch32_224": dict(img=224, patch=32, dim=768, depth=12, heads=12),
+    "vit_base_patch16_384": dict(img=384, patch=16, dim=768, depth=12, heads=12),
     "vit_tiny_test": dict(img=64, patch=16, dim=128, depth=2, heads=2),   # reduced member for fast parity tests
     "vit_small_test": dict(img=64, patch=16, dim=256, depth=2, heads=4),  # reduced member inside the fp8 GEMM envelope (dim 256)
+    "vit_tiny192_test": dict(img=64, patch=16, dim=192, depth=2, heads=3),       # reduced ViT-Tiny width (T = 17)
+    "vit_tiny192_p32_test": dict(img=96, patch=32, dim=192, depth=1, heads=3),   # ... with 32-pixel patches (T = 10)
+}
+# DeiT (no distillation token) is the same module under timm's VisionTransformer keys: the names differ in the pretrained weights only
+_ALIASES = {
+    "deit_tiny_patch16_224": "vit_tiny_patch16_224",
+    "deit_small_patch16_224": "vit_small_patch16_224",
+    "deit_base_patch16_224": "vit_base_patch16_224",
 }
 
 
+def vit_members():
+    """The names create_backbone answers for this family (reduced test members left out)."""
+    return sorted(k for k in list(_VITS) + list(_ALIASES) if not k.endswith("_test"))
+
+
 def create_vit(name: str):
-    cfg = _VITS.get(name)
+    cfg = _VITS.get(_ALIASES.get(name, name))
     return HipViT(**cfg) if cfg else None
