@@ -8,18 +8,12 @@ HipEngine through libnkbhip, never by torch.nn forward methods.
 """
 from __future__ import annotations
 
-import os
 from typing import List, Optional, Sequence
 
 import torch
 from torch import nn
 
 from .hipnet import HipEngine
-
-# bn1 -> relu -> maxpool of the stem as one kernel each way (0 = separate kernels, for A/B measurements)
-_FUSED_STEM_TAIL = True
-# forward: projection-shortcut convolution on the side stream, next to the block's main branch
-_SIDE_SHORTCUT = True
 
 
 class _ParamOnly(nn.Module):
@@ -155,33 +149,27 @@ class HipResNet(_ParamOnly):
         hip.im2row(eng.d, img, col, N, C, H, W, 3, 3, 2, 1, kp)
         x = eng.conv_bn("stem0", col, c0, b0, True, None, train, col_input=True).view(N, P, Q, c0.out_channels)
         x = eng.conv_bn("stem1", x, c1, b1, True, None, train)
-        x = eng.conv_bn("stem", x, c2, self.bn1, True, None, train, pool=_FUSED_STEM_TAIL)
-        if not _FUSED_STEM_TAIL:
-            x = eng.maxpool("pool", x, train)
-        return x
+        return eng.conv_bn("stem", x, c2, self.bn1, True, None, train, pool=True)
 
     # ---- execution plan ---------------------------------------------------------------
     def run_forward(self, eng: HipEngine, img: torch.Tensor, train: bool) -> torch.Tensor:
         from . import hip
         N, C, H, W = img.shape
         conv = self.conv1
-        fused = _FUSED_STEM_TAIL
+        # bn1 -> ReLU -> max-pool close the stem convolution as one kernel each way (pool=True)
         if self.deep_stem:
             x = self._deep_stem_forward(eng, img, train)
-            fused = True                                   # (the helper has pooled already)
         elif eng.packed_stem(conv):
             xp = eng.ws.get("stem.xp", (N, H, (W + 1) // 2 * 2, 4), eng.T)
             hip.stem_pack(eng.d, img, xp, N, C, H, W)
-            x = eng.conv_bn("stem", xp, conv, self.bn1, True, None, train, pool=fused, stem_packed=(N, H, W))
+            x = eng.conv_bn("stem", xp, conv, self.bn1, True, None, train, pool=True, stem_packed=(N, H, W))
         else:
             R, st, pad = conv.kernel_size[0], conv.stride[0], conv.padding[0]
             P, Q = (H + 2 * pad - R) // st + 1, (W + 2 * pad - R) // st + 1
             kp = eng.kpad(C * R * R)
             col = eng.ws.get("stem.col", (N, P, Q, kp), eng.T)
             hip.im2row(eng.d, img, col, N, C, H, W, R, R, st, pad, kp)
-            x = eng.conv_bn("stem", col, conv, self.bn1, True, None, train, col_input=True, pool=fused)
-        if not fused:
-            x = eng.maxpool("pool", x, train)
+            x = eng.conv_bn("stem", col, conv, self.bn1, True, None, train, col_input=True, pool=True)
         all_blocks = list(self.blocks())
         nblocks = len(all_blocks)
         for bi, (name, blk) in enumerate(all_blocks):
@@ -207,17 +195,13 @@ class HipResNet(_ParamOnly):
                     if pool is not None:                   # avg_down, stride-2 block: the 1x1 convolution reads the pooled map
                         src = eng.avgpool2(key + "p", src, train)
                     box["r"] = eng.conv_bn(key, src, cv, bn, False, None, train, defer_apply=True)
-                if _SIDE_SHORTCUT:
-                    eng.on_side(shortcut)
-                else:
-                    shortcut()
+                eng.on_side(shortcut)
             # Gram form of the closing stage (hipnet._conv_bn_gram): every bottleneck but the last — its backward needs the masked
             # output gradient + sums that the NEXT block's conv1 data gradient leaves (can_fuse_residual_bn_backward)
             for k, (cv, bn) in enumerate(stages[:-1]):
                 x = eng.conv_bn(f"{name}.{k}", x, cv, bn, True, None, train, gram_out=want_gram and k == len(stages) - 2)
             if blk.downsample is not None and proj is None:
-                if _SIDE_SHORTCUT:
-                    eng.join_side()
+                eng.join_side()
                 short, s_scale, s_shift = box["r"]
                 short_affine = (s_scale, s_shift) if s_scale is not None else None     # None: eval mode, already normalised
             cv, bn = stages[-1]
@@ -294,11 +278,7 @@ class HipResNet(_ParamOnly):
             if on_done is not None and name.endswith(".0"):
                 on_done(getattr(self, name.split(".")[0]))
         eng.begin_block(-1)
-        if eng.saved["stem"]["pool_idx"] is not None:
-            gc = eng.bn_pool_backward("stem", g, "t0")
-        else:
-            g = eng.maxpool_backward("pool", g, "mp")
-            gc = eng.bn_backward("stem", g, "t0")
+        gc = eng.bn_pool_backward("stem", g, "t0")
         if self.deep_stem:
             # plain chain: narrow data gradient -> BatchNorm backward, twice; the three weight gradients go to the side stream
             ga = eng.conv_backward("stem", gc, "a2")

@@ -17,11 +17,8 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from . import hip
 from .backbones import _ParamOnly
 from .hipnet import HipEngine
-
-_GELU_KEEP_DERIV = True   # forward stores gelu'(pre); backward = fc2-dgrad epilogue multiply (as vit.py)
 
 
 class _Mlp(_ParamOnly):
@@ -96,22 +93,13 @@ class HipConvNeXt(_ParamOnly):
         GELU, mlp.drop2 before the layer scale, head.drop on the embedding.  Stochastic depth is off (drop_path_rate = 0)."""
         for k in [k for k in eng.saved if k.endswith("_drop")]:
             del eng.saved[k]                                 # masks of a previous step must not leak into this backward
-        B, Cin, Hh, Ww = img.shape
-        cv, a = self.stem[0], eng.arena
+        B, _, Hh, Ww = img.shape
+        cv = self.stem[0]
         ps = cv.kernel_size[0]
         H, W = Hh // ps, Ww // ps
         if H < 8 or W < 8:
             raise RuntimeError(f"ConvNeXt needs images of at least {8 * ps}x{8 * ps} (three 2x2 downsamples), got {Hh}x{Ww}")
-        D0 = self.dims[0]
-        K = Cin * ps * ps
-        kp = eng.kpad(K)
-        col = eng.ws.get("stem.col", (B * H * W, kp), eng.T)
-        hip.im2row(eng.d, img, col, B, Cin, Hh, Ww, ps, ps, ps, 0, kp)
-        tok = eng.ws.get("stem.tok", (B * H * W, D0), eng.T)
-        hip.conv_gemm(eng.d, 0, col, eng.w_fwd(cv.weight), tok, N=B * H * W, H=1, W=1, Cin=kp, ldx=kp, P=1, Q=1, Cout=D0, ldy=D0,
-                      bias=a.param_flat(cv.bias))
-        if train:
-            eng.saved["stem"] = dict(col=col, B=B, H=H, W=W, kp=kp, K=K)
+        tok, _ = eng.patch_embed("stem", img, cv, train)
         x = eng.layernorm("stem.ln", tok, self.stem[1], train)
         for si, st in enumerate(self.stages):
             C = self.dims[si]
@@ -124,11 +112,7 @@ class HipConvNeXt(_ParamOnly):
                 k, mlp = f"s{si}.b{bi}", blk.mlp
                 y = eng.dwconv(f"{k}.dw", x, blk.conv_dw, B, H, W, train)
                 h = eng.layernorm(f"{k}.ln", y, blk.norm, train)
-                keep = _GELU_KEEP_DERIV and not (train and mlp.drop1.p > 0)
-                u = eng.linear_gelu_keep_derivative(f"{k}.fc1", f"{k}.act", h, mlp.fc1, train) if keep else None
-                if u is None:
-                    u = eng.gelu(f"{k}.act", eng.linear(f"{k}.fc1", h, mlp.fc1, train), train, keep_derivative=keep)
-                u = eng.dropout(f"{k}.mlp_drop", u, mlp.drop1.p, train)
+                u = eng.mlp_gelu_fc1(k, h, mlp, train)
                 z = eng.linear(f"{k}.fc2", u, mlp.fc2, train)
                 z = eng.dropout(f"{k}.mlp2_drop", z, mlp.drop2.p, train)
                 x = eng.layer_scale(f"{k}.ls", z, blk.gamma, x, train)
@@ -141,7 +125,6 @@ class HipConvNeXt(_ParamOnly):
         so the data-parallel reducer can start exchanging it while backward continues."""
         sv = eng.saved["stem"]
         B = sv["B"]
-        a = eng.arena
         D = self.dims[-1]
         g_emb = eng.dropout_backward("head_drop", g_emb, "gemb")
         gp = eng.layernorm_backward("head.ln", g_emb, eng.scratch("gpool", (B, D)), D)
@@ -161,12 +144,7 @@ class HipConvNeXt(_ParamOnly):
                 k = f"s{si}.b{bi}"
                 gz = eng.layer_scale_backward(f"{k}.ls", gx, "gz")             # branch gradient; the residual path keeps gx
                 g2 = eng.dropout_backward(f"{k}.mlp2_drop", gz, "g2")
-                if "gp" in eng.saved[f"{k}.act"]:
-                    d_a = eng.linear_backward_through_saved_derivative(f"{k}.fc2", f"{k}.act", g2, "da")
-                else:
-                    d_u = eng.dropout_backward(f"{k}.mlp_drop", eng.linear_backward(f"{k}.fc2", g2, "du"), "du2")
-                    d_a = eng.gelu_backward(f"{k}.act", d_u, "da")
-                d_h = eng.linear_backward(f"{k}.fc1", d_a, "dh")
+                d_h = eng.mlp_gelu_fc1_backward(k, g2)
                 gy = eng.layernorm_backward(f"{k}.ln", d_h, eng.scratch("gy", (M, C)), C)
                 gx = eng.dwconv_backward(f"{k}.dw", gy, "gx", add=gx)
                 eng.end_block(unit)
@@ -183,17 +161,7 @@ class HipConvNeXt(_ParamOnly):
         eng.begin_block(-1)
         D0, rows = self.dims[0], sv["B"] * sv["H"] * sv["W"]
         d_tok = eng.layernorm_backward("stem.ln", gx, eng.scratch("dtok", (rows, D0)), D0)
-        cv = self.stem[0]
-        kp, K = sv["kp"], sv["K"]
-        if kp == K:
-            eng.wgrad(d_tok, sv["col"], a.grad_flat(cv.weight), N=rows, H=1, W=1, Cin=kp, ldx=kp, P=1, Q=1, Cout=D0, lddy=D0,
-                      dbias=a.grad_flat(cv.bias))
-        else:
-            dwp = eng.ws.get("stem.dwpad", (D0, kp), torch.float32)
-            hip.zero_(dwp)
-            eng.wgrad(d_tok, sv["col"], dwp, N=rows, H=1, W=1, Cin=kp, ldx=kp, P=1, Q=1, Cout=D0, lddy=D0)
-            hip.add2d(dwp, a.grad_flat(cv.weight), D0, K, kp, K)
-            eng.colsum2d(d_tok, a.grad_flat(cv.bias), rows, D0, D0)
+        eng.patch_embed_backward("stem", d_tok, self.stem[0])
         if on_done is not None:
             on_done(self.stem)
 

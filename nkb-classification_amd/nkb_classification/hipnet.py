@@ -27,25 +27,11 @@ _FUSED_RES_BN_BWD = os.environ.get("NKB_FUSED_RES_BNBWD", "1") != "0"
 _RELU_BITS = os.environ.get("NKB_RELU_BITS", "1") != "0"
 _ATTN_FUSED_BWD = True  # whole attention backward in one kernel
 _ATTN_FUSED_DQ = True   # dQ inside the attention backward-dS kernel
-_SPLITK = True              # split-K for skinny Linear layers with K >= 32768
 _EVAL_FOLD = os.environ.get("NKB_EVAL_FOLD", "1") != "0"     # eval mode: BatchNorm folded into the conv (one launch per stage)
 # weight / bias gradients through per-split slabs + an ordered second stage instead of fp32 atomics: bit-identical across runs
 _FP8_FUSED_QUANT = os.environ.get("NKB_FP8_FUSED_QUANT", "1") != "0"   # fp8 operands written by the producing kernel's epilogue
-_FP8_WGRAD = True   # fp8 mode: weight gradients of the fp8 Linear layers on the fp8 kernel too
-# bias gradients summed inside the e5m2 quantisation pass of dY (main stream) instead of a column-sum pass on the side stream:
-# measured slower on unicom ViT-L/14 (65.0 vs 63.9 ms/step: the side stream has the slack, the main stream does not) — off
-_FP8_COLSUM = False
-_WPREP_FROM_SHADOW = True
-# LayerNorm dgamma / dbeta reduction (two small launches) on the side stream instead of in the backward chain: measured neutral
-# (unicom fp8 50.8-51.4 vs 50.9-51.3 ms, ViT-B/16 35.65-35.74 vs 35.74-35.78) — the other stream fills those gaps anyway.  Off.
-_LN_REDUCE_SIDE = False
 _LN_BWD_SCALED_COPY = True   # bf16: LayerNorm backward writes scale[b] * dx as well
-_ROWSCALE_EPILOGUE = True   # bf16: drop-path scale in the residual GEMM epilogue
-_GELU_EPILOGUE = True   # gelu + gelu' in the fc1 epilogue of the eight-phase core
-_FP8_ATTN_COLSUM = True   # qkv bias gradient from the attention backward kernel's stores
 _FP8_LN_BWD_QUANT = True   # LayerNorm backward writes the next Linear backward's fp8 operand
-_FP8_EPI_COLSUM = True   # fc1's bias gradient from the fc2 data gradient's epilogue
-_FP8_MASK_BITS = True   # fp8 step: ReLU6 output kept as fp8 operand + mask bits, no bf16 copy
 _DET_WGRAD = os.environ.get("NKB_DET_WGRAD", "1") != "0"
 # Gram form of the bottleneck closing stage (csrc/grambn.hip): BatchNorm statistics of conv3's output from the Gram matrix of its
 # input, normalisation + shortcut + ReLU in conv3's epilogue, backward through R = g^T a and one K-concatenated data gradient — the
@@ -142,7 +128,7 @@ class HipEngine:
             jobs, njobs, nblocks = self._wjobs
             # (bf16: the transposes read the optimizer's bf16 shadow of the masters — the values they would round to, half the bytes)
             hip.wprep_multi(self.d, a.flat_param, jobs, njobs, nblocks,
-                            shadow=a.shadow if (self.T == torch.bfloat16 and _WPREP_FROM_SHADOW) else None)
+                            shadow=a.shadow if self.T == torch.bfloat16 else None)
         if self.fp8 and self.T == torch.bfloat16 and need_dgrad:
             self._refresh_fp8_weights()
         self._dgrad_ready = need_dgrad
@@ -230,7 +216,10 @@ class HipEngine:
         st = self._fp8_state(key, kind, x)
         n = x.numel()
         q = self.ws.get(key + ".q", tuple(x.shape), torch.uint8)
-        if (_FP8_COLSUM or row_scale is not None) and colsum is not None and self._fp8_colsum_ok(x):
+        # the fused pass only where a per-sample scale needs it: summing every bias gradient inside the quantisation pass of dY (main
+        # stream) instead of a column-sum pass on the side stream measured slower on unicom ViT-L/14 (65.0 vs 63.9 ms/step: the side
+        # stream has the slack, the main stream does not)
+        if row_scale is not None and colsum is not None and self._fp8_colsum_ok(x):
             rows, C = x.shape
             work = self.ws.at_least("f8.colsum." + self._stream_tag(), hip.fp8_quantize_colsum_workspace(rows, C), torch.float32)
             hip.fp8_quantize_colsum(kind, x, rows, C, C, st, q, colsum, work,
@@ -592,17 +581,7 @@ class HipEngine:
         return dx, (stats2, tiles2)
 
     def _splitk_ok(self, rows: int, ci: int, co: int) -> bool:
-        return _SPLITK and rows <= 256 and ci >= 32768 and co > 64 and ci % (self.kte * 32) == 0
-
-    def maxpool(self, key: str, x: torch.Tensor, train: bool) -> torch.Tensor:
-        N, H, W, C = x.shape
-        P, Q = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-        y = self.ws.get(key + ".y", (N, P, Q, C), self.T)
-        idx = self.ws.get(key + ".idx", (N, P, Q, C), torch.uint8)
-        hip.maxpool(self.d, False, x, y, idx, N, H, W, C)
-        if train:
-            self.saved[key] = dict(idx=idx, in_shape=(N, H, W, C))
-        return y
+        return rows <= 256 and ci >= 32768 and co > 64 and ci % (self.kte * 32) == 0
 
     def avgpool2(self, key: str, x: torch.Tensor, train: bool) -> torch.Tensor:
         """AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False): the pool in front of an avg_down projection shortcut."""
@@ -643,8 +622,7 @@ class HipEngine:
                 seed = hip.fresh_seed()
                 hip.dropout(self.d, False, emb, None, d_emb, mask, B * E, drop_p, seed)
                 n_t = w.shape[0]
-                hip.conv_gemm(self.d, 0, d_emb, self.w_fwd(w), logits[:, lo_c:], N=B, H=1, W=1, Cin=E, ldx=E, P=1, Q=1,
-                              Cout=n_t, ldy=ctot, bias=a.param_flat(hb[t]), out_f32=True)
+                self._gemm(d_emb, self.w_fwd(w), logits[:, lo_c:], B, E, n_t, ldy=ctot, bias=a.param_flat(hb[t]), out_f32=True)
                 dropped.append(d_emb); masks.append(mask); lo_c += n_t
             self.saved["head"] = dict(emb=emb, ctot=ctot, dropped=dropped, masks=masks, drop_p=drop_p)
             return logits
@@ -653,8 +631,7 @@ class HipEngine:
         bo = a.offset_of(hb[0])
         ball = a.flat_param[bo:bo + ctot]
         logits = out if out is not None else torch.empty(B, ctot, device=self.device, dtype=torch.float32)
-        hip.conv_gemm(self.d, 0, emb, wall, logits, N=B, H=1, W=1, Cin=E, ldx=E, P=1, Q=1, Cout=ctot, ldy=ctot,
-                      bias=ball, out_f32=True)
+        self._gemm(emb, wall, logits, B, E, ctot, bias=ball, out_f32=True)
         if train:
             self.saved["head"] = dict(emb=emb, ctot=ctot)
         return logits
@@ -775,14 +752,13 @@ class HipEngine:
             glogits = glogits.contiguous()
         hip.pad_cast(self.d, glogits, dl, B, ctot, ctot, cp)
         lo = a.offset_of(hw[0])
-        self.wgrad(dl, emb, a.flat_grad[lo:lo + ctot * E], N=B, H=1, W=1, Cin=E, ldx=E, P=1, Q=1,
-                       Cout=ctot, lddy=cp)
+        self._gemm_wgrad(dl, emb, a.flat_grad[lo:lo + ctot * E], B, E, ctot, lddy=cp)
         bo = a.offset_of(hb[0])
         hip.colsum(self.d, dl, a.flat_grad[bo:bo + ctot], B, ctot, cp)
         if not need_demb:
             return None
         g = self.ws.get("head.demb", (B, E), self.T)
-        hip.conv_gemm(self.d, 0, dl, self._wd["head"], g, N=B, H=1, W=1, Cin=cp, ldx=cp, P=1, Q=1, Cout=E, ldy=E)
+        self._gemm(dl, self._wd["head"], g, B, cp, E)
         return g
 
     def _head_backward_dropout(self, glogits: torch.Tensor, need_demb: bool) -> Optional[torch.Tensor]:
@@ -802,14 +778,13 @@ class HipEngine:
             cpt = self.kpad(n_t)
             dl = self.ws.get(f"head.dl{t}", (B, cpt), self.T)
             hip.pad_cast(self.d, glogits[:, lo_c:], dl, B, n_t, ctot, cpt)
-            self.wgrad(dl, sv["dropped"][t], a.grad_flat(w), N=B, H=1, W=1, Cin=E, ldx=E, P=1, Q=1, Cout=n_t,
-                           lddy=cpt)
+            self._gemm_wgrad(dl, sv["dropped"][t], a.grad_flat(w), B, E, n_t, lddy=cpt)
             hip.colsum(self.d, dl, a.grad_flat(hb[t]), B, n_t, cpt)
             if need_demb:
                 wt = self.ws.get(f"head.wt{t}", (E, cpt), self.T)
                 hip.wprep(self.d, a.param_flat(w), wt, n_t, 1, E, cpt, 1)
                 gt = self.ws.get(f"head.demb{t}", (B, E), self.T)
-                hip.conv_gemm(self.d, 0, dl, wt, gt, N=B, H=1, W=1, Cin=cpt, ldx=cpt, P=1, Q=1, Cout=E, ldy=E)
+                self._gemm(dl, wt, gt, B, cpt, E)
                 # through the head's own dropout mask, accumulated over heads
                 hip.dropout(self.d, True, gt, g_total if t > 0 else None, g_total, sv["masks"][t], B * E, p, 0)
             lo_c += n_t
@@ -819,13 +794,6 @@ class HipEngine:
         N, H, W, C = self.saved[key]["in_shape"]
         dx = self.scratch(slot, (N, H, W, C))
         hip.avgpool(self.d, True, g, dx, N, H * W, C)
-        return dx
-
-    def maxpool_backward(self, key: str, g: torch.Tensor, slot: str) -> torch.Tensor:
-        sv = self.saved[key]
-        N, H, W, C = sv["in_shape"]
-        dx = self.scratch(slot, (N, H, W, C))
-        hip.maxpool(self.d, True, g, dx, sv["idx"], N, H, W, C)
         return dx
 
     def bn_backward(self, key: str, g_y: torch.Tensor, slot: str, write_masked: bool = False,
@@ -923,16 +891,7 @@ class HipEngine:
             self.on_side(packed_wgrad)
             return None
         if sv["col_input"]:
-            kp = geom["Cin"]
-            co = geom["Cout"]
-            K = w.shape[1] * w.shape[2] * w.shape[3]
-            dwp = self.ws.get(key + ".dwpad", (co, kp), torch.float32)
-
-            def stem_wgrad():
-                hip.zero_(dwp)
-                self.wgrad(g_c, sv["x"], dwp, N=geom["N"], H=1, W=1, Cin=kp, ldx=kp, P=1, Q=1, Cout=co, lddy=co)
-                hip.add2d(dwp, a.grad_flat(w), co, K, kp, K)
-            self.on_side(stem_wgrad)
+            self.on_side(lambda: self._wgrad_kpadded(key, g_c, sv["x"], w, geom["N"], geom["Cin"], geom["Cout"]))
             return None
         self.on_side(lambda: self.wgrad(
             g_c, sv["x"], a.grad_flat(w), N=geom["N"], H=geom["H"], W=geom["W"], Cin=geom["Cin"], ldx=geom["ldx"],
@@ -945,8 +904,7 @@ class HipEngine:
             # 1x1 stride-2 shortcut: its input gradient is non-zero only on the even (h, w) grid, so it is computed as a
             # plain GEMM on the output grid [N,P,Q] and later folded in by the consumer's epilogue (add_hw)
             dx = self.scratch(slot, (N, geom["P"], geom["Q"], ci))
-            hip.conv_gemm(self.d, 0, g_c, self._wd[id(w)], dx, N=N * geom["P"] * geom["Q"], H=1, W=1, Cin=geom["Cout"],
-                          ldx=geom["Cout"], P=1, Q=1, Cout=ci, ldy=ci)
+            self._gemm(g_c, self._wd[id(w)], dx, N * geom["P"] * geom["Q"], geom["Cout"], ci)
             return dx
         dx = self.scratch(slot, (N, H, W, ci))
         if self.narrow3(w, geom["stride"], geom["pad"]):
@@ -1003,6 +961,51 @@ class HipEngine:
         return dx
 
     # ------------------------------------------------------------------ transformer ops ----
+    def _gemm(self, x, w, y, M: int, K: int, N: int, ldy: Optional[int] = None, **epilogue):
+        """y[M][N] = x[M][K] . w[N][K]^T (+ epilogue): to nkb_conv_gemm a plain product is a 1x1 convolution over M pixels."""
+        hip.conv_gemm(self.d, 0, x, w, y, N=M, H=1, W=1, Cin=K, ldx=K, P=1, Q=1, Cout=N, ldy=N if ldy is None else ldy, **epilogue)
+
+    def _gemm_wgrad(self, g, x, dw, M: int, K: int, N: int, dbias=None, lddy: Optional[int] = None, assign: bool = False):
+        """dw[N][K] (+)= g[M][N]^T . x[M][K], dbias[N] += column sums of g: the weight gradient of _gemm, through wgrad()."""
+        self.wgrad(g, x, dw, dbias=dbias, assign=assign, N=M, H=1, W=1, Cin=K, ldx=K, P=1, Q=1, Cout=N, lddy=N if lddy is None else lddy)
+
+    def _wgrad_kpadded(self, prefix: str, g, col, w, rows: int, kp: int, co: int):
+        """Weight gradient against an im2row matrix whose rows are padded from K to kp columns: the product lands in an fp32 scratch
+        [co][kp], whose first K columns are then added into the arena."""
+        K = w[0].numel()
+        dwp = self.ws.get(prefix + ".dwpad", (co, kp), torch.float32)
+        hip.zero_(dwp)
+        self._gemm_wgrad(g, col, dwp, rows, kp, co)
+        hip.add2d(dwp, self.arena.grad_flat(w), co, K, kp, K)
+
+    def patch_embed(self, prefix: str, img: torch.Tensor, proj: nn.Conv2d, train: bool):
+        """Patch embedding (kernel = stride, no padding) as im2row + GEMM with bias.  Returns the token matrix [B*gh*gw, D] and
+        the grid (gh, gw); what the model adds to the tokens (class token, position embedding, LayerNorm) stays with the model."""
+        B, C, Hh, Ww = img.shape
+        D, ps = proj.weight.shape[0], proj.kernel_size[0]
+        gh, gw = Hh // ps, Ww // ps
+        rows, K = B * gh * gw, C * ps * ps
+        kp = self.kpad(K)
+        col = self.ws.get(prefix + ".col", (rows, kp), self.T)
+        hip.im2row(self.d, img, col, B, C, Hh, Ww, ps, ps, ps, 0, kp)
+        tok = self.ws.get(prefix + ".tok", (rows, D), self.T)
+        self._gemm(col, self.w_fwd(proj.weight), tok, rows, kp, D, bias=self.arena.param_flat(proj.bias))
+        if train:
+            self.saved[prefix] = dict(col=col, B=B, H=gh, W=gw, kp=kp, K=K)
+        return tok, (gh, gw)
+
+    def patch_embed_backward(self, prefix: str, d_tok: torch.Tensor, proj: nn.Conv2d):
+        """Weight and bias gradient of patch_embed(prefix); d_tok: [B*gh*gw, D].  K a multiple of the k-tile (16- and 32-pixel
+        patches): straight into the arena; otherwise (14-pixel patches, K = 588) through the padded scratch."""
+        sv = self.saved[prefix]
+        rows, D = d_tok.shape
+        kp, a = sv["kp"], self.arena
+        if kp == sv["K"]:
+            self._gemm_wgrad(d_tok, sv["col"], a.grad_flat(proj.weight), rows, kp, D, dbias=a.grad_flat(proj.bias))
+        else:
+            self._wgrad_kpadded(prefix, d_tok, sv["col"], proj.weight, rows, kp, D)
+            self.colsum2d(d_tok, a.grad_flat(proj.bias), rows, D, D)
+
     def linear(self, key: str, x: torch.Tensor, lin: nn.Linear, train: bool, add: Optional[torch.Tensor] = None,
                row_scale=None) -> torch.Tensor:
         """y = x @ W^T + b (+ add); x: [M, K] in the compute dtype.  row_scale = (per-sample scale [B], rows per sample), with
@@ -1020,30 +1023,28 @@ class HipEngine:
             if train:
                 self.saved[key] = dict(x=x, lin=lin, xq=xq, sx=sx)
             return y
-        if row_scale is not None and add is not None and _ROWSCALE_EPILOGUE and self.T == torch.bfloat16 \
-                and hip.linear_gelu_fused_ok(self.d, M, K, N):
+        if row_scale is not None and add is not None and self.T == torch.bfloat16 and hip.linear_gelu_fused_ok(self.d, M, K, N):
             # stochastic depth in the residual epilogue of the eight-phase core (no second pass over the branch output)
             hip.linear_residual_scaled(self.d, x, self.w_fwd(lin.weight), bias, add, row_scale[0], row_scale[1], y, M, K, N)
         elif row_scale is not None:
-            hip.conv_gemm(self.d, 0, x, self.w_fwd(lin.weight), y, N=M, H=1, W=1, Cin=K, ldx=K, P=1, Q=1, Cout=N, ldy=N, bias=bias)
+            self._gemm(x, self.w_fwd(lin.weight), y, M, K, N, bias=bias)
             out = self.ws.get(key + ".ys", (M, N), self.T)
             hip.scale_rows(self.d, y, add, out, row_scale[0], M // row_scale[1], row_scale[1] * N)
             y = out
         else:
-            hip.conv_gemm(self.d, 0, x, self.w_fwd(lin.weight), y, N=M, H=1, W=1, Cin=K, ldx=K, P=1, Q=1, Cout=N, ldy=N,
-                          bias=bias, add=add, ldadd=N if add is not None else 0)
+            self._gemm(x, self.w_fwd(lin.weight), y, M, K, N, bias=bias, add=add, ldadd=N if add is not None else 0)
         if train:
             self.saved[key] = dict(x=x, lin=lin)
         return y
 
     @staticmethod
     def _fp8_wgrad_ok(sv, M: int, K: int, N: int) -> bool:
-        return _FP8_WGRAD and sv.get("xq") is not None and hip.wgrad_fp8_workspace(M, K, N) > 0
+        return sv.get("xq") is not None and hip.wgrad_fp8_workspace(M, K, N) > 0
 
     def _linear_wgrad(self, sv, g: torch.Tensor, gq=None, sg=None, bias_done: bool = False):
         """Weight / bias gradient of a Linear on the side stream.  With both fp8 copies at hand (the forward operand xq and the
-        data gradient's operand gq) the contraction runs on the fp8 kernel (NKB_FP8_WGRAD=0: bf16); the bias gradient is then
-        the column sum of the unquantised g."""
+        data gradient's operand gq) the contraction runs on the fp8 kernel; the bias gradient is then the column sum of the
+        unquantised g (unless the pass that made gq summed the columns already: bias_done)."""
         x, lin = sv["x"], sv["lin"]
         M, K = x.shape
         N = lin.weight.shape[0]
@@ -1059,8 +1060,7 @@ class HipEngine:
                     self.colsum2d(g, dbias, M, N, N)
             self.on_side(run)
             return
-        self.on_side(lambda: self.wgrad(g, x, a.grad_flat(lin.weight), N=M, H=1, W=1, Cin=K, ldx=K, P=1, Q=1, Cout=N, lddy=N,
-                                        dbias=dbias))
+        self.on_side(lambda: self._gemm_wgrad(g, x, a.grad_flat(lin.weight), M, K, N, dbias=dbias))
 
     def _branch_gradient(self, sv, lin, g: torch.Tensor, g_scale, M: int, K: int, N: int, slot: str):
         """g_scale = (per-sample scale, rows per sample) of a stochastic-depth branch: the gradient that enters the Linear is
@@ -1078,20 +1078,27 @@ class HipEngine:
         hip.scale_rows(self.d, g, None, dx, g_scale[0], M // g_scale[1], g_scale[1] * g.shape[1])
         return dx, None
 
-    def linear_backward(self, key: str, g: torch.Tensor, slot: Optional[str], add: Optional[torch.Tensor] = None, g_scale=None):
+    def _linear_backward_front(self, key: str, g: torch.Tensor, g_scale, dgrad: bool, allow_fp8: bool = True):
+        """What every Linear backward starts with: the branch gradient, its e5m2 copy in the fp8 step (made when the data gradient
+        is wanted — dgrad — or the forward kept an fp8 operand for the weight gradient) and the weight / bias gradient on the side
+        stream.  Returns (lin, M, K, N, fp8, g, gq, sg) for the data gradient that follows."""
         sv = self.saved[key]
         x, lin = sv["x"], sv["lin"]
         M, K = x.shape
         N = lin.weight.shape[0]
-        fp8 = self._fp8_linear_ok(lin, M)
+        fp8 = allow_fp8 and self._fp8_linear_ok(lin, M)
         g, rsc = self._branch_gradient(sv, lin, g, g_scale, M, K, N, "gs_" + key.rsplit(".", 1)[-1])   # (read later by the side stream)
         gq = sg = None
         bias_done = False
-        if fp8 and (slot is not None or (_FP8_WGRAD and sv.get("xq") is not None)):
+        if fp8 and (dgrad or sv.get("xq") is not None):
             # one e5m2 copy serves the data and the weight gradient; the pass that makes it also sums the columns (bias gradient)
             want = self.arena.grad_flat(lin.bias) if (lin.bias is not None and self._fp8_wgrad_ok(sv, M, K, N)) else None
             gq, sg, bias_done = self._fp8_operand(key + ".f8g", g, hip.E5M2, colsum=want, row_scale=rsc)
         self._linear_wgrad(sv, g, gq, sg, bias_done)
+        return lin, M, K, N, fp8, g, gq, sg
+
+    def linear_backward(self, key: str, g: torch.Tensor, slot: Optional[str], add: Optional[torch.Tensor] = None, g_scale=None):
+        lin, M, K, N, fp8, g, gq, sg = self._linear_backward_front(key, g, g_scale, slot is not None)
         if slot is None:
             return None
         dx = self.scratch(slot, (M, K))
@@ -1099,8 +1106,7 @@ class HipEngine:
             _, wdq, sw = self._f8w[id(lin.weight)]
             hip.gemm_fp8(1, gq, wdq, dx, M, N, K, deq_x=sg[1:2], deq_w=sw[1:2], add=add, ldadd=K if add is not None else 0)
         else:
-            hip.conv_gemm(self.d, 0, g, self._wd[id(lin.weight)], dx, N=M, H=1, W=1, Cin=N, ldx=N, P=1, Q=1, Cout=K, ldy=K,
-                          add=add, ldadd=K if add is not None else 0)
+            self._gemm(g, self._wd[id(lin.weight)], dx, M, N, K, add=add, ldadd=K if add is not None else 0)
         return dx
 
     def linear_relu6(self, key: str, x: torch.Tensor, lin: nn.Linear, train: bool, q_for: Optional[str] = None,
@@ -1119,7 +1125,7 @@ class HipEngine:
             wq, _, sw = self._f8w[id(lin.weight)]
             out = self._fp8_produce(q_for, (M, N), hip.E4M3) if train else None
             bits = None
-            if (out and _FP8_MASK_BITS and consumer is not None and _FP8_WGRAD and M % 128 == 0 and N % 8 == 0
+            if (out and consumer is not None and M % 128 == 0 and N % 8 == 0
                     and self._fp8_linear_ok(consumer, M) and hip.wgrad_fp8_workspace(M, N, consumer.weight.shape[0]) > 0):
                 bits = self.ws.get(key + ".bits", (M, N // 8), torch.uint8)
             hip.gemm_fp8(0, xq, wq, None if bits is not None else u, M, K, N, deq_x=sx[1:2], deq_w=sw[1:2], bias=bias, relu=2,
@@ -1127,34 +1133,23 @@ class HipEngine:
             if train:
                 self.saved[key] = dict(x=x, lin=lin, u=None if bits is not None else u, ubits=bits, xq=xq, sx=sx)
             return u
-        else:
-            hip.conv_gemm(self.d, 0, x, self.w_fwd(lin.weight), u, N=M, H=1, W=1, Cin=K, ldx=K, P=1, Q=1, Cout=N, ldy=N,
-                          bias=bias, relu=2)
+        self._gemm(x, self.w_fwd(lin.weight), u, M, K, N, bias=bias, relu=2)
         if train:
             self.saved[key] = dict(x=x, lin=lin, u=u)
         return u
 
-    def linear_backward_through_relu6(self, key_next: str, key_act: str, g: torch.Tensor, slot: str,
-                                      q_for: Optional[str] = None, g_scale=None) -> torch.Tensor:
-        """For u = relu6(pre), y = u @ W2^T + b2: weight/bias gradient of W2 (side stream) and d_pre = (g @ W2) masked by
-        0 < u < 6 in one GEMM epilogue."""
-        sv = self.saved[key_next]
-        x, lin = sv["x"], sv["lin"]          # x = u (ReLU6 output), lin = fc2
-        M, K = x.shape
-        N = lin.weight.shape[0]
-        fp8 = self._fp8_linear_ok(lin, M)
-        g, rsc = self._branch_gradient(sv, lin, g, g_scale, M, K, N, "gs_" + key_next.rsplit(".", 1)[-1])
-        gq = sg = None
-        bias_done = False
-        if fp8:
-            want = self.arena.grad_flat(lin.bias) if (lin.bias is not None and self._fp8_wgrad_ok(sv, M, K, N)) else None
-            gq, sg, bias_done = self._fp8_operand(key_next + ".f8g", g, hip.E5M2, colsum=want, row_scale=rsc)
-        self._linear_wgrad(sv, g, gq, sg, bias_done)
+    def linear_backward_through_act(self, key_next: str, key_act: str, g: torch.Tensor, slot: str,
+                                    q_for: Optional[str] = None, g_scale=None) -> torch.Tensor:
+        """For u = act(pre), y = u @ W2^T + b2 (key_next: fc2, K = hidden width): weight/bias gradient of W2 (side stream) and
+        d_pre = (g @ W2) * act'(pre) in one GEMM epilogue.  The activation is what the forward pass saved under key_act: `gp`, the
+        derivative gelu'(pre) itself (multiplied in; bf16 kernels in the fp8 step too, as no fp8 epilogue takes it), or the ReLU6
+        output `u` / its mask bits `ubits` (d_pre masked by 0 < u < 6)."""
+        sva = self.saved[key_act]
+        lin, M, K, N, fp8, g, gq, sg = self._linear_backward_front(key_next, g, g_scale, True, allow_fp8="gp" not in sva)
         d_pre = self.scratch(slot, (M, K))
         if fp8:
             _, wdq, sw = self._f8w[id(lin.weight)]
             out = self._fp8_produce(q_for, (M, K), hip.E5M2)
-            sva = self.saved[key_act]
             ubits = sva.get("ubits") if out else None         # (the bit form needs the quantised second output)
             if ubits is None and sva["u"] is None:
                 raise RuntimeError("the ReLU6 output was kept as mask bits only, but this data gradient cannot consume them")
@@ -1162,7 +1157,7 @@ class HipEngine:
             # d_pre is its bias gradient: the epilogue sums the columns too and d_pre is never stored in bf16.
             lin1 = sva["lin"]
             csum = work = None
-            if (_FP8_EPI_COLSUM and ubits is not None and lin1.bias is not None and M % 256 == 0
+            if (ubits is not None and lin1.bias is not None and M % 256 == 0
                     and self._fp8_wgrad_ok(sva, M, lin1.weight.shape[1], K)):
                 csum = self.arena.grad_flat(lin1.bias)
                 work = self.ws.at_least("f8.epicolsum", (M // 256) * K, torch.float32)
@@ -1171,28 +1166,18 @@ class HipEngine:
                          aux=None if ubits is not None else sva["u"], aux_mode=1, mask_in=ubits, colsum=csum, colsum_work=work,
                          yq=out[0] if out else None, q_state=out[1] if out else None, q_kind=out[2] if out else 0)
         else:
-            hip.linear_gelu(self.d, 3, g, self._wd[id(lin.weight)], None, self.saved[key_act]["u"], d_pre, None, M, N, K)
+            act, aux = (4, sva["gp"]) if "gp" in sva else (3, sva["u"])
+            hip.linear_gelu(self.d, act, g, self._wd[id(lin.weight)], None, aux, d_pre, None, M, N, K)
         return d_pre
-
-    def linear_gelu(self, key: str, x: torch.Tensor, lin: nn.Linear, train: bool) -> torch.Tensor:
-        """u = gelu(x @ W^T + b) with the GELU in the GEMM epilogue; the pre-activation is kept for backward."""
-        M, K = x.shape
-        N = lin.weight.shape[0]
-        pre = self.ws.get(key + ".pre", (M, N), self.T)
-        u = self.ws.get(key + ".y", (M, N), self.T)
-        hip.linear_gelu(self.d, 1, x, self.w_fwd(lin.weight), self.arena.param_flat(lin.bias), None, u, pre, M, K, N)
-        if train:
-            self.saved[key] = dict(x=x, lin=lin, pre=pre)
-        return u
 
     def linear_gelu_keep_derivative(self, key: str, key_act: str, x: torch.Tensor, lin: nn.Linear, train: bool):
         """u = gelu(x @ W^T + b) AND gelu'(pre) from the fc1 GEMM's epilogue (the pre-activation is never stored; the separate
         elementwise pass over it is gone); saved like linear() + gelu(keep_derivative=True), so the backward pass is
-        linear_backward_through_saved_derivative + linear_backward.  Returns None when the shape is not one of the eight-phase
+        linear_backward_through_act + linear_backward.  Returns None when the shape is not one of the eight-phase
         core's (the caller then takes the two-kernel path)."""
         M, K = x.shape
         N = lin.weight.shape[0]
-        if not (_GELU_EPILOGUE and train and self.T == torch.bfloat16 and lin.bias is not None and not self._fp8_linear_ok(lin, M)
+        if not (train and self.T == torch.bfloat16 and lin.bias is not None and not self._fp8_linear_ok(lin, M)
                 and hip.linear_gelu_fused_ok(self.d, M, K, N)):
             return None
         u = self.ws.get(key_act + ".y", (M, N), self.T)
@@ -1202,20 +1187,24 @@ class HipEngine:
         self.saved[key_act] = dict(gp=gp)
         return u
 
-    def linear_backward_through_gelu(self, key_next: str, key_act: str, g: torch.Tensor, slot: str) -> torch.Tensor:
-        """For u = gelu(pre), y = u @ W2^T + b2: weight/bias gradient of W2 (side stream) and d_pre = (g @ W2) * gelu'(pre)
-        in one GEMM epilogue (the separate GELU-backward pass and the d_u tensor disappear)."""
-        sv = self.saved[key_next]
-        x, lin = sv["x"], sv["lin"]          # x = u (gelu output), lin = fc2
-        M, K = x.shape                      # K = hidden width
-        N = lin.weight.shape[0]
-        a = self.arena
-        self.on_side(lambda: self.wgrad(
-            g, x, a.grad_flat(lin.weight), N=M, H=1, W=1, Cin=K, ldx=K, P=1, Q=1, Cout=N, lddy=N,
-            dbias=a.grad_flat(lin.bias) if lin.bias is not None else None))
-        d_pre = self.scratch(slot, (M, K))
-        hip.linear_gelu(self.d, 2, g, self._wd[id(lin.weight)], None, self.saved[key_act]["pre"], d_pre, None, M, N, K)
-        return d_pre
+    def mlp_gelu_fc1(self, prefix: str, h: torch.Tensor, mlp, train: bool) -> torch.Tensor:
+        """First half of a timm Mlp (ViT and ConvNeXt blocks): fc1 -> exact-erf GELU -> drop1, under the keys <prefix>.fc1, .act and
+        .mlp_drop.  gelu'(pre) is kept in place of the pre-activation (from the fc1 epilogue where the shape allows it, else from
+        the GELU pass) unless drop1 is active: the dropout mask sits between fc2's data gradient and the GELU's then."""
+        keep = not (train and mlp.drop1.p > 0)
+        u = self.linear_gelu_keep_derivative(prefix + ".fc1", prefix + ".act", h, mlp.fc1, train) if keep else None
+        if u is None:
+            u = self.gelu(prefix + ".act", self.linear(prefix + ".fc1", h, mlp.fc1, train), train, keep_derivative=keep)
+        return self.dropout(prefix + ".mlp_drop", u, mlp.drop1.p, train)
+
+    def mlp_gelu_fc1_backward(self, prefix: str, g2: torch.Tensor) -> torch.Tensor:
+        """g2: gradient of <prefix>.fc2's output.  Backward of fc2 and of mlp_gelu_fc1(prefix); returns the gradient of fc1's input."""
+        if "gp" in self.saved[prefix + ".act"]:
+            d_a = self.linear_backward_through_act(prefix + ".fc2", prefix + ".act", g2, "da")
+        else:
+            d_u = self.dropout_backward(prefix + ".mlp_drop", self.linear_backward(prefix + ".fc2", g2, "du"), "du2")
+            d_a = self.gelu_backward(prefix + ".act", d_u, "da")
+        return self.linear_backward(prefix + ".fc1", d_a, "dh")
 
     def layernorm(self, key: str, x: torch.Tensor, ln: nn.LayerNorm, train: bool, rows: Optional[int] = None,
                   x_stride: Optional[int] = None, q_for: Optional[str] = None) -> torch.Tensor:
@@ -1247,23 +1236,11 @@ class HipEngine:
         D = ln.weight.shape[0]
         rows = sv["rows"]
         a = self.arena
-        # The parameter-gradient half (two small launches that sum the per-block partial rows) only feeds dgamma / dbeta (/ a bias
-        # gradient): it goes to the side stream with the weight gradients instead of sitting in the backward chain.  Its partial
-        # rows then live in a workspace of this LayerNorm's own (per block parity, like the gradient scratch: begin_block waits
-        # for the side-stream readers before a set is reused).
-        split = _LN_REDUCE_SIDE and self.overlap_wgrad
-        work = self.ws.at_least("ln.work" + (self._suffix + "." + key.rsplit(".", 1)[-1] if split else ""), hip.layernorm_ws(D),
-                                torch.float32)
-        dg, db = a.grad_flat(ln.weight), a.grad_flat(ln.bias)
+        work = self.ws.at_least("ln.work", hip.layernorm_ws(D), torch.float32)
 
         def launch(colsum=None, **kw):
-            if not split:
-                hip.layernorm_bwd(self.d, g, D, sv["x"], sv["xs"], a.param_flat(ln.weight), sv["mean"], sv["rstd"], add, out,
-                                  out_stride, dg, db, rows, D, workspace=work, colsum=colsum, **kw)
-                return
-            hip.layernorm_bwd(self.d, g, D, sv["x"], sv["xs"], a.param_flat(ln.weight), sv["mean"], sv["rstd"], add, out,
-                              out_stride, None, None, rows, D, workspace=work, **kw)
-            self.on_side(lambda: hip.layernorm_param_reduce(work, rows, D, 3 if colsum is not None else 2, dg, db, colsum))
+            hip.layernorm_bwd(self.d, g, D, sv["x"], sv["xs"], a.param_flat(ln.weight), sv["mean"], sv["rstd"], add, out, out_stride,
+                              a.grad_flat(ln.weight), a.grad_flat(ln.bias), rows, D, workspace=work, colsum=colsum, **kw)
         q = None
         if consumer is not None and self.fp8 and _FP8_LN_BWD_QUANT and _FP8_FUSED_QUANT and self.T == torch.bfloat16:
             svc = self.saved.get(consumer)
@@ -1305,7 +1282,7 @@ class HipEngine:
 
     def gelu(self, key: str, x: torch.Tensor, train: bool, keep_derivative: bool = False) -> torch.Tensor:
         """keep_derivative: the forward pass also stores gelu'(x), overwriting x (the pre-activation is not needed again);
-        the backward pass is then linear_backward_through_saved_derivative instead of gelu_backward."""
+        the backward pass is then linear_backward_through_act instead of gelu_backward."""
         y = self.ws.get(key + ".y", x.shape, self.T)
         if train and keep_derivative:
             hip.gelu_fwd_dgelu(self.d, x, y, x, x.numel())
@@ -1316,38 +1293,10 @@ class HipEngine:
             self.saved[key] = dict(x=x)
         return y
 
-    def linear_backward_through_saved_derivative(self, key_next: str, key_act: str, g: torch.Tensor, slot: str) -> torch.Tensor:
-        """For u = act(pre), y = u @ W2^T + b2 with act'(pre) kept by the forward pass: weight/bias gradient of W2 (side
-        stream) and d_pre = (g @ W2) * act'(pre) in one GEMM epilogue."""
-        sv = self.saved[key_next]
-        x, lin = sv["x"], sv["lin"]
-        M, K = x.shape
-        N = lin.weight.shape[0]
-        a = self.arena
-        self.on_side(lambda: self.wgrad(
-            g, x, a.grad_flat(lin.weight), N=M, H=1, W=1, Cin=K, ldx=K, P=1, Q=1, Cout=N, lddy=N,
-            dbias=a.grad_flat(lin.bias) if lin.bias is not None else None))
-        d_pre = self.scratch(slot, (M, K))
-        hip.linear_gelu(self.d, 4, g, self._wd[id(lin.weight)], None, self.saved[key_act]["gp"], d_pre, None, M, N, K)
-        return d_pre
-
     def gelu_backward(self, key: str, g: torch.Tensor, slot: str) -> torch.Tensor:
         x = self.saved[key]["x"]
         dx = self.scratch(slot, x.shape)
         hip.gelu(self.d, x, g, dx, x.numel())
-        return dx
-
-    def relu6(self, key: str, x: torch.Tensor, train: bool) -> torch.Tensor:
-        y = self.ws.get(key + ".y", x.shape, self.T)
-        hip.relu6(self.d, x, None, y, x.numel())
-        if train:
-            self.saved[key] = dict(x=x)
-        return y
-
-    def relu6_backward(self, key: str, g: torch.Tensor, slot: str) -> torch.Tensor:
-        x = self.saved[key]["x"]
-        dx = self.scratch(slot, x.shape)
-        hip.relu6(self.d, x, g, dx, x.numel())
         return dx
 
     def _ones(self, n: int) -> torch.Tensor:
@@ -1468,7 +1417,7 @@ class HipEngine:
             # dQ, dK, dV in one kernel per layer: P and dS never reach HBM
             out = self._fp8_produce(q_for, tuple(qkv.shape), hip.E5M2) if self.fp8 else None       # the qkv gradients' fp8 operand
             csum = work = None
-            if out and _FP8_ATTN_COLSUM and q_for.endswith(".f8g") and q_for[:-4] in self.saved:
+            if out and q_for.endswith(".f8g") and q_for[:-4] in self.saved:
                 # the qkv projection takes both gradients from the fp8 copy: its bias gradient — the column sums of d_qkv — is the
                 # only other reader of the bf16 tensor, and comes out of this kernel's stores instead of a pass over d_qkv
                 svc = self.saved[q_for[:-4]]

@@ -20,16 +20,12 @@ of HBM the activations of the B=128 configuration are simply kept.
 """
 from __future__ import annotations
 
-import os
-
 import torch
 from torch import nn
 
 from . import hip
 from .backbones import _ParamOnly
 from .hipnet import HipEngine
-
-_FUSED_RELU6 = True   # ReLU6 in the fc1 epilogue, its mask in the fc2 data gradient
 
 
 class _PatchEmbedding(_ParamOnly):
@@ -114,23 +110,13 @@ class HipUnicomViT(_ParamOnly):
     def run_forward(self, eng: HipEngine, img: torch.Tensor, train: bool) -> torch.Tensor:
         for k in [k for k in eng.saved if k.endswith(".dp1") or k.endswith(".dp2")]:
             del eng.saved[k]                                 # stochastic-depth draws of a previous step
-        B, C, Hh, Ww = img.shape
+        B, _, Hh, Ww = img.shape
         if Hh != self.img or Ww != self.img:
             raise RuntimeError(f"this ViT expects {self.img}x{self.img} inputs (pos_embed is fixed), got {Hh}x{Ww}")
-        pr = self.patch_embed.proj
-        D, ps, T = self.dim, self.patch, self.patch_embed.num_patches
-        K = C * ps * ps
-        kp = eng.kpad(K)
-        a = eng.arena
-        col = eng.ws.get("pe.col", (B * T, kp), eng.T)
-        hip.im2row(eng.d, img, col, B, C, Hh, Ww, ps, ps, ps, 0, kp)
-        tok = eng.ws.get("pe.tok", (B * T, D), eng.T)
-        hip.conv_gemm(eng.d, 0, col, eng.w_fwd(pr.weight), tok, N=B * T, H=1, W=1, Cin=kp, ldx=kp, P=1, Q=1, Cout=D,
-                      ldy=D, bias=a.param_flat(pr.bias))
+        D, T = self.dim, self.patch_embed.num_patches
+        tok, _ = eng.patch_embed("pe", img, self.patch_embed.proj, train)
         x = eng.ws.get("pe.x", (B * T, D), eng.T)
-        hip.vit_assemble(eng.d, False, tok, None, a.param_flat(self.pos_embed), x, B, T, D)
-        if train:
-            eng.saved["pe"] = dict(col=col, B=B, T=T, kp=kp, K=K)
+        hip.vit_assemble(eng.d, False, tok, None, eng.arena.param_flat(self.pos_embed), x, B, T, D)
         for i, blk in enumerate(self.blocks):
             at, mlp = blk.attn, blk.mlp
             dp = self._dp(blk) if train else 0.0
@@ -142,10 +128,8 @@ class HipUnicomViT(_ParamOnly):
             else:
                 x = eng.linear(f"b{i}.proj", o, at.proj, train, add=x)
             h = eng.layernorm(f"b{i}.ln2", x, blk.norm2, train, q_for=f"b{i}.fc1.f8x")
-            if _FUSED_RELU6:
-                u = eng.linear_relu6(f"b{i}.fc1", h, mlp.fc1, train, q_for=f"b{i}.fc2.f8x", consumer=mlp.fc2)
-            else:
-                u = eng.relu6(f"b{i}.act", eng.linear(f"b{i}.fc1", h, mlp.fc1, train), train)
+            # ReLU6 in the fc1 epilogue, its mask in the fc2 data gradient
+            u = eng.linear_relu6(f"b{i}.fc1", h, mlp.fc1, train, q_for=f"b{i}.fc2.f8x", consumer=mlp.fc2)
             if dp > 0:
                 x = eng.linear(f"b{i}.fc2", u, mlp.fc2, train, add=x, row_scale=(eng.drop_path_scale(f"b{i}.dp2", dp, B), T))
             else:
@@ -157,8 +141,7 @@ class HipUnicomViT(_ParamOnly):
         return e2.view(B, self.num_features)
 
     def run_backward(self, eng: HipEngine, g_emb: torch.Tensor, on_done=None):
-        sv = eng.saved["pe"]
-        B, T = sv["B"], sv["T"]
+        B, T = eng.saved["pe"]["B"], self.patch_embed.num_patches
         D = self.dim
         M = B * T
         a = eng.arena
@@ -180,11 +163,7 @@ class HipUnicomViT(_ParamOnly):
             blk = self.blocks[i]
             eng.begin_block(i)
             gs2 = eng.drop_path_gscale(f"b{i}.dp2", M)                       # branch gradient = scale * gx; the residual path keeps gx
-            if _FUSED_RELU6:
-                d_a = eng.linear_backward_through_relu6(f"b{i}.fc2", f"b{i}.fc1", gx, "da", q_for=f"b{i}.fc1.f8g", g_scale=gs2)
-            else:
-                d_u = eng.linear_backward(f"b{i}.fc2", gx, "du", g_scale=gs2)
-                d_a = eng.relu6_backward(f"b{i}.act", d_u, "da")
+            d_a = eng.linear_backward_through_act(f"b{i}.fc2", f"b{i}.fc1", gx, "da", q_for=f"b{i}.fc1.f8g", g_scale=gs2)
             d_h = eng.linear_backward(f"b{i}.fc1", d_a, "dh")
             gmid = eng.layernorm_backward(f"b{i}.ln2", d_h, eng.scratch("gmid", (M, D)), D, add=gx,
                                           consumer=f"b{i}.proj", consumer_dp=f"b{i}.dp1")
@@ -200,17 +179,7 @@ class HipUnicomViT(_ParamOnly):
         eng.begin_block(-1)
         # embedding: d_pos = sum_b gx[b]; the token gradient is gx itself (no class token)
         eng.colsum2d(gx, a.grad_flat(self.pos_embed), B, T * D, T * D)
-        pr = self.patch_embed.proj
-        kp, K = sv["kp"], sv["K"]
-        if kp == K:
-            eng.wgrad(gx, sv["col"], a.grad_flat(pr.weight), N=M, H=1, W=1, Cin=kp, ldx=kp, P=1, Q=1, Cout=D,
-                           lddy=D, dbias=a.grad_flat(pr.bias))
-        else:
-            dwp = eng.ws.get("pe.dwpad", (D, kp), torch.float32)
-            hip.zero_(dwp)
-            eng.wgrad(gx, sv["col"], dwp, N=M, H=1, W=1, Cin=kp, ldx=kp, P=1, Q=1, Cout=D, lddy=D)
-            hip.add2d(dwp, a.grad_flat(pr.weight), D, K, kp, K)
-            eng.colsum2d(gx, a.grad_flat(pr.bias), M, D, D)
+        eng.patch_embed_backward("pe", gx, self.patch_embed.proj)
         if on_done is not None:
             on_done(self.patch_embed)
             on_done([self.pos_embed])

@@ -7,17 +7,12 @@ bias, exact-erf GELU, pre-norm residual blocks, x[:, 0] of the final norm as the
 """
 from __future__ import annotations
 
-import os
-
 import torch
 from torch import nn
 
 from . import hip
 from .backbones import _ParamOnly
 from .hipnet import HipEngine
-
-_GELU_KEEP_DERIV = True   # forward stores gelu'(pre); backward = fc2-dgrad epilogue multiply
-_FUSED_GELU = False   # measured: erf in the GEMM epilogue costs more than the pass it saves (66.3 vs 65.9 ms)
 
 
 class _PatchEmbed(_ParamOnly):
@@ -91,26 +86,14 @@ class HipViT(_ParamOnly):
         mlp.drop2 before the residual additions, mlp.drop1 after the GELU, head_drop on the pooled embedding."""
         for k in [k for k in eng.saved if k.endswith(".drop") or k.endswith("_drop")]:
             del eng.saved[k]                                 # masks of a previous step must not leak into this backward
-        B, C, Hh, Ww = img.shape
+        B, _, Hh, Ww = img.shape
         if Hh != self.img or Ww != self.img:
             raise RuntimeError(f"this ViT expects {self.img}x{self.img} inputs (pos_embed is fixed), got {Hh}x{Ww}")
-        pr = self.patch_embed.proj
-        D, ps = self.num_features, self.patch
-        gh = Hh // ps
-        npatch = gh * gh
-        T = npatch + 1
-        K = C * ps * ps
-        kp = eng.kpad(K)
-        col = eng.ws.get("pe.col", (B * npatch, kp), eng.T)
-        hip.im2row(eng.d, img, col, B, C, Hh, Ww, ps, ps, ps, 0, kp)
-        tok = eng.ws.get("pe.tok", (B * npatch, D), eng.T)
+        D, T = self.num_features, self.pos_embed.shape[1]
         a = eng.arena
-        hip.conv_gemm(eng.d, 0, col, eng.w_fwd(pr.weight), tok, N=B * npatch, H=1, W=1, Cin=kp, ldx=kp, P=1, Q=1, Cout=D,
-                      ldy=D, bias=a.param_flat(pr.bias))
+        tok, _ = eng.patch_embed("pe", img, self.patch_embed.proj, train)
         x = eng.ws.get("pe.x", (B * T, D), eng.T)
         hip.vit_assemble(eng.d, False, tok, a.param_flat(self.cls_token), a.param_flat(self.pos_embed), x, B, T, D)
-        if train:
-            eng.saved["pe"] = dict(col=col, B=B, T=T, kp=kp, K=K)
         x = eng.dropout("pos_drop", x, self.pos_drop.p, train)
         for i, blk in enumerate(self.blocks):
             at, mlp = blk.attn, blk.mlp
@@ -122,14 +105,7 @@ class HipViT(_ParamOnly):
             else:
                 x = eng.linear(f"b{i}.proj", o, at.proj, train, add=x)
             h = eng.layernorm(f"b{i}.ln2", x, blk.norm2, train, q_for=f"b{i}.fc1.f8x")
-            if _FUSED_GELU:
-                u = eng.linear_gelu(f"b{i}.fc1", h, mlp.fc1, train)        # GELU fused into the fc1 epilogue
-            else:
-                keep = _GELU_KEEP_DERIV and not (train and mlp.drop1.p > 0)
-                u = eng.linear_gelu_keep_derivative(f"b{i}.fc1", f"b{i}.act", h, mlp.fc1, train) if keep else None
-                if u is None:
-                    u = eng.gelu(f"b{i}.act", eng.linear(f"b{i}.fc1", h, mlp.fc1, train), train, keep_derivative=keep)
-            u = eng.dropout(f"b{i}.mlp_drop", u, mlp.drop1.p, train)
+            u = eng.mlp_gelu_fc1(f"b{i}", h, mlp, train)
             if train and mlp.drop2.p > 0:
                 x = eng.dropout(f"b{i}.mlp2_drop", eng.linear(f"b{i}.fc2", u, mlp.fc2, train), mlp.drop2.p, train, add=x)
             else:
@@ -139,8 +115,7 @@ class HipViT(_ParamOnly):
         return eng.dropout("head_drop", emb, self.head_drop.p, train)
 
     def run_backward(self, eng: HipEngine, g_emb: torch.Tensor, on_done=None):
-        sv = eng.saved["pe"]
-        B, T = sv["B"], sv["T"]
+        B, T = eng.saved["pe"]["B"], self.pos_embed.shape[1]
         D = self.num_features
         M = B * T
         a = eng.arena
@@ -155,15 +130,7 @@ class HipViT(_ParamOnly):
             blk = self.blocks[i]
             eng.begin_block(i)
             g2 = eng.dropout_backward(f"b{i}.mlp2_drop", gx, "g2")       # branch gradient; the residual path keeps gx
-            if _FUSED_GELU:   # gelu' fused into the fc2 data-gradient epilogue
-                d_a = eng.linear_backward_through_gelu(f"b{i}.fc2", f"b{i}.fc1", g2, "da")
-            else:
-                if "gp" in eng.saved[f"b{i}.act"]:
-                    d_a = eng.linear_backward_through_saved_derivative(f"b{i}.fc2", f"b{i}.act", g2, "da")
-                else:
-                    d_u = eng.dropout_backward(f"b{i}.mlp_drop", eng.linear_backward(f"b{i}.fc2", g2, "du"), "du2")
-                    d_a = eng.gelu_backward(f"b{i}.act", d_u, "da")
-            d_h = eng.linear_backward(f"b{i}.fc1", d_a, "dh")
+            d_h = eng.mlp_gelu_fc1_backward(f"b{i}", g2)
             gmid = eng.layernorm_backward(f"b{i}.ln2", d_h, eng.scratch("gmid", (M, D)), D, add=gx)
             d_o = eng.linear_backward(f"b{i}.proj", eng.dropout_backward(f"b{i}.proj_drop", gmid, "g1"), "do")
             d_qkv = eng.attention_backward(f"b{i}.attn", d_o, "dqkv", q_for=f"b{i}.qkv.f8g")
@@ -178,20 +145,9 @@ class HipViT(_ParamOnly):
         # embedding: d_pos = sum_b gx[b], d_cls = sum_b gx[b, 0], d_tok = gx[:, 1:], then the patch projection
         eng.colsum2d(gx, a.grad_flat(self.pos_embed), B, T * D, T * D)
         eng.colsum2d(gx, a.grad_flat(self.cls_token), B, D, T * D)
-        npatch = T - 1
-        d_tok = eng.scratch("dtok", (B * npatch, D))
+        d_tok = eng.scratch("dtok", (B * (T - 1), D))
         hip.vit_assemble(eng.d, True, d_tok, None, None, gx, B, T, D)
-        pr = self.patch_embed.proj
-        kp, K = sv["kp"], sv["K"]
-        if kp == K:
-            eng.wgrad(d_tok, sv["col"], a.grad_flat(pr.weight), N=B * npatch, H=1, W=1, Cin=kp, ldx=kp, P=1,
-                           Q=1, Cout=D, lddy=D, dbias=a.grad_flat(pr.bias))
-        else:
-            dwp = eng.ws.get("pe.dwpad", (D, kp), torch.float32)
-            hip.zero_(dwp)
-            eng.wgrad(d_tok, sv["col"], dwp, N=B * npatch, H=1, W=1, Cin=kp, ldx=kp, P=1, Q=1, Cout=D, lddy=D)
-            hip.add2d(dwp, a.grad_flat(pr.weight), D, K, kp, K)
-            eng.colsum2d(d_tok, a.grad_flat(pr.bias), B * npatch, D, D)
+        eng.patch_embed_backward("pe", d_tok, self.patch_embed.proj)
         if on_done is not None:
             on_done(self.patch_embed)
             on_done([self.cls_token, self.pos_embed])

@@ -497,6 +497,37 @@ def test_unicom_fp8_train_step_tracks_bf16_and_oracle():
     assert c8 > 0.97 and c16 > 0.995
 
 
+def test_unicom_fp8_mask_bits_without_a_consumer_is_a_loud_error(monkeypatch):
+    """fp8 step of the reduced unicom ViT at 16 images (M = 256 rows: mask bits and epilogue column sums both open): from the
+    second step on fc1 keeps its ReLU6 output as mask bits only.  A fc2 data gradient that cannot write its quantised second output
+    (here: the scaling state of its consumer site is gone) cannot read the bits either — an error from the host, before any launch,
+    not a gradient computed without the mask."""
+    from nkb_classification import model as model_mod
+    monkeypatch.setattr(model_mod, "_PLANS", False)          # the Python path decides at every step
+    cfg_model = dict(model="unicom ViT-small-test", pretrained=False, backbone_dropout=0.0, classifier_dropout=0.0,
+                     classifier_initialization="kaiming_normal_", task="single")
+    crit = get_loss(dict(task="single", type="CrossEntropyLoss"), DEV)
+    g = torch.Generator().manual_seed(4)
+    x, y = torch.randn(16, 3, 56, 56, generator=g).to(DEV), torch.randint(0, 4, (16,), generator=g).to(DEV)
+    torch.manual_seed(0)
+    model = get_model(dict(cfg_model), ["a", "b", "c", "d"], DEV)
+    model.train()
+    model.fp8_linear = True
+    for k in range(3):
+        for p in model.parameters():
+            p.grad = None
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            loss = crit(model(x), y)
+        if k < 2:
+            loss.backward()
+    eng = model._engines[torch.bfloat16]
+    assert eng.saved["b1.fc1"]["ubits"] is not None and eng.saved["b1.fc1"]["u"] is None
+    del eng._f8act["b1.fc1.f8g"]
+    with pytest.raises(RuntimeError, match="kept as mask bits only"):
+        loss.backward()
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("mode", ["bf16", "fp8"])
 def test_unicom_branch_gradient_from_layernorm_backward_equals_separate_pass(mode, monkeypatch):
     """Stochastic depth active (rate 0.5) on the reduced unicom ViT (dim 256, two blocks): the branch gradient scale[b] * dx that
