@@ -61,6 +61,7 @@ class HipEngine:
         self._convs: List[nn.Module] = []
         self._stems: List[nn.Module] = []
         self._heads = None
+        self.derived = None                        # model hook run(engine) with the weight refresh: engine-owned copies of parameters
         self._bn_scratch_off = 0
         # weight gradients run on a side HIP stream next to the dgrad -> BN-backward chain of the main stream (both are
         # latency-bound at ~20 % MFMA busy, so they overlap almost additively); see begin_block()/on_side()
@@ -122,6 +123,8 @@ class HipEngine:
             if buf is None:
                 buf = self._wpad[id(w)] = runtime.empty(w.shape[0], self.kpad(K), device=self.device, dtype=self.T)
             hip.wprep(self.d, a.param_flat(w), buf, w.shape[0], 1, K, buf.shape[1], 0)
+        if self.derived is not None and self._wver != a.version:
+            self.derived(self)
         if need_dgrad:
             if self._wjobs is None:
                 self._wjobs = self._build_dgrad_jobs()
@@ -989,7 +992,8 @@ class HipEngine:
         col = self.ws.get(prefix + ".col", (rows, kp), self.T)
         hip.im2row(self.d, img, col, B, C, Hh, Ww, ps, ps, ps, 0, kp)
         tok = self.ws.get(prefix + ".tok", (rows, D), self.T)
-        self._gemm(col, self.w_fwd(proj.weight), tok, rows, kp, D, bias=self.arena.param_flat(proj.bias))
+        bias = self.arena.param_flat(proj.bias) if proj.bias is not None else None      # (none in the pre_norm ViT members)
+        self._gemm(col, self.w_fwd(proj.weight), tok, rows, kp, D, bias=bias)
         if train:
             self.saved[prefix] = dict(col=col, B=B, H=gh, W=gw, kp=kp, K=K)
         return tok, (gh, gw)
@@ -1000,11 +1004,13 @@ class HipEngine:
         sv = self.saved[prefix]
         rows, D = d_tok.shape
         kp, a = sv["kp"], self.arena
+        dbias = a.grad_flat(proj.bias) if proj.bias is not None else None
         if kp == sv["K"]:
-            self._gemm_wgrad(d_tok, sv["col"], a.grad_flat(proj.weight), rows, kp, D, dbias=a.grad_flat(proj.bias))
+            self._gemm_wgrad(d_tok, sv["col"], a.grad_flat(proj.weight), rows, kp, D, dbias=dbias)
         else:
             self._wgrad_kpadded(prefix, d_tok, sv["col"], proj.weight, rows, kp, D)
-            self.colsum2d(d_tok, a.grad_flat(proj.bias), rows, D, D)
+            if dbias is not None:
+                self.colsum2d(d_tok, dbias, rows, D, D)
 
     def linear(self, key: str, x: torch.Tensor, lin: nn.Linear, train: bool, add: Optional[torch.Tensor] = None,
                row_scale=None) -> torch.Tensor:

@@ -155,6 +155,7 @@ class _HipClassifier(nn.Module):
             eng.register(em.gemm_convs(), em.stem_convs(), [h.weight for h in heads], [h.bias for h in heads])
             if hasattr(em, "fp8_linears"):
                 eng.fp8_candidates = em.fp8_linears()
+            eng.derived = getattr(em, "refresh_derived", None)
             self._engines[dtype] = eng
         return eng
 

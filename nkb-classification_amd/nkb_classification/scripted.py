@@ -110,42 +110,62 @@ class _Mlp(nn.Module):
         return self.fc2(torch.nn.functional.gelu(self.fc1(x)))
 
 
-class _Block(nn.Module):
-    def __init__(self, dim: int, heads: int, mlp_ratio: float):
+class _LayerScale(nn.Module):
+    def __init__(self, dim: int, init_values: float):
         super().__init__()
-        self.norm1 = nn.LayerNorm(dim, eps=1e-6)
-        self.attn = _Attention(dim, heads)
-        self.norm2 = nn.LayerNorm(dim, eps=1e-6)
-        self.mlp = _Mlp(dim, int(dim * mlp_ratio))
+        self.gamma = nn.Parameter(init_values * torch.ones(dim))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x = x + self.attn(self.norm1(x))
-        return x + self.mlp(self.norm2(x))
+        return x * self.gamma
+
+
+class _Block(nn.Module):
+    def __init__(self, dim: int, heads: int, mlp_ratio: float, ln_eps: float = 1e-6, init_values: Optional[float] = None):
+        super().__init__()
+        self.norm1 = nn.LayerNorm(dim, eps=ln_eps)
+        self.attn = _Attention(dim, heads)
+        self.ls1 = _LayerScale(dim, init_values) if init_values is not None else nn.Identity()
+        self.norm2 = nn.LayerNorm(dim, eps=ln_eps)
+        self.mlp = _Mlp(dim, int(dim * mlp_ratio))
+        self.ls2 = _LayerScale(dim, init_values) if init_values is not None else nn.Identity()
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        x = x + self.ls1(self.attn(self.norm1(x)))
+        return x + self.ls2(self.mlp(self.norm2(x)))
 
 
 class _PatchEmbed(nn.Module):
-    def __init__(self, patch: int, dim: int):
+    def __init__(self, patch: int, dim: int, bias: bool = True):
         super().__init__()
-        self.proj = nn.Conv2d(3, dim, patch, patch)
+        self.proj = nn.Conv2d(3, dim, patch, patch, bias=bias)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.proj(x).flatten(2).transpose(1, 2)
 
 
 class _ViT(nn.Module):
-    def __init__(self, img: int, patch: int, dim: int, depth: int, heads: int, mlp_ratio: float = 4.0):
+    """timm VisionTransformer with its pre_norm / init_values (LayerScale) / no_embed_class options (nkb_classification/vit.py)."""
+
+    def __init__(self, img: int, patch: int, dim: int, depth: int, heads: int, mlp_ratio: float = 4.0, pre_norm: bool = False,
+                 ln_eps: float = 1e-6, init_values: Optional[float] = None, no_embed_class: bool = False):
         super().__init__()
         self.num_features = dim
-        self.patch_embed = _PatchEmbed(patch, dim)
+        self.no_embed_class = no_embed_class
+        self.patch_embed = _PatchEmbed(patch, dim, bias=not pre_norm)
         self.cls_token = nn.Parameter(torch.zeros(1, 1, dim))
-        self.pos_embed = nn.Parameter(torch.zeros(1, (img // patch) ** 2 + 1, dim))
-        self.blocks = nn.Sequential(*[_Block(dim, heads, mlp_ratio) for _ in range(depth)])
-        self.norm = nn.LayerNorm(dim, eps=1e-6)
+        self.pos_embed = nn.Parameter(torch.zeros(1, (img // patch) ** 2 + (0 if no_embed_class else 1), dim))
+        self.norm_pre = nn.LayerNorm(dim, eps=ln_eps) if pre_norm else nn.Identity()
+        self.blocks = nn.Sequential(*[_Block(dim, heads, mlp_ratio, ln_eps, init_values) for _ in range(depth)])
+        self.norm = nn.LayerNorm(dim, eps=ln_eps)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         x = self.patch_embed(x)
-        x = torch.cat((self.cls_token.expand(x.shape[0], -1, -1), x), dim=1) + self.pos_embed
-        return self.norm(self.blocks(x))[:, 0]
+        cls = self.cls_token.expand(x.shape[0], -1, -1)
+        if self.no_embed_class:
+            x = torch.cat((cls, x + self.pos_embed), dim=1)
+        else:
+            x = torch.cat((cls, x), dim=1) + self.pos_embed
+        return self.norm(self.blocks(self.norm_pre(x)))[:, 0]
 
 
 class _UnicomAttention(nn.Module):
@@ -291,7 +311,9 @@ def _backbone_like(hip_backbone) -> nn.Module:
         return _UnicomViT(hip_backbone.img, hip_backbone.patch, hip_backbone.dim, hip_backbone.num_features,
                           len(hip_backbone.blocks), hip_backbone.heads)
     if getattr(hip_backbone, "family", "") == "vit":
-        return _ViT(hip_backbone.img, hip_backbone.patch, hip_backbone.num_features, len(hip_backbone.blocks), hip_backbone.heads)
+        return _ViT(hip_backbone.img, hip_backbone.patch, hip_backbone.num_features, len(hip_backbone.blocks), hip_backbone.heads,
+                    pre_norm=hip_backbone.pre_norm, ln_eps=hip_backbone.ln_eps, init_values=hip_backbone.init_values,
+                    no_embed_class=hip_backbone.no_embed_class)
     if getattr(hip_backbone, "family", "") == "convnext":
         return _ConvNeXt(list(hip_backbone.depths), list(hip_backbone.dims))
     layers = [len(getattr(hip_backbone, f"layer{i}")) for i in (1, 2, 3, 4)]
