@@ -424,7 +424,16 @@ int nkb_loss_backward(const float* probs, int ldp, const long long* target, cons
                       const float* grad_out, int grad_out_per_row, int B, int C, float* dlogits, int ldd,
                       nkb_stream_t stream);
 
-/* Fused flat-arena optimizer step. kind: 0 adam, 1 nadam (decoupled wd), 2 radam, 3 sgd.
+/* Fused flat-arena optimizer step. kind: 0 adam, 1 nadam (decoupled wd), 2 radam, 3 sgd; any other kind is refused.
+ * c0..c2 are the step-dependent scalars of torch.optim's formulas, computed by the host (utils._step_scalars).
+ * c3 != 0 with kind 0 or 2: decoupled weight decay, w *= 1 - lr * wd first and no wd * w term in the gradient
+ * (kind 0 is then torch.optim.AdamW, kind 2 RAdam(decoupled_weight_decay=True)); kind 1 ignores c3.
+ * kind 3: beta1 is the momentum and c0 the factor on the incoming gradient in the buffer update: 1 - dampening, or 1 on the
+ * step where torch clones the gradient into a fresh buffer. beta1 != 0 with c0 != 0 is the momentum form: it reads and writes
+ * m, the momentum buffer, and never v (may be NULL): m = beta1 * m + c0 * grad; c1 != 0 selects Nesterov (grad + beta1 * m is
+ * applied instead of m) and is refused outside the momentum form. beta1 == 0 or c0 == 0 is plain SGD and touches neither m nor v
+ * (both may be NULL): callers from before the momentum form hand kind 3 Adam's betas with zeros in c0..c3, and keep their
+ * result. Kinds 0..2 need both m and v: a NULL one is refused.
  * skip_flag (device float, may be NULL): the launch does nothing when *skip_flag != 0 — the skipped step of
  * GradScaler.step (engine.py:59) decided on the device. */
 int nkb_optim_step(int kind, float* p, const float* g, float* m, float* v, void* shadow_bf16, long long n, float lr,

@@ -1,8 +1,8 @@
 // Fused flat-arena optimizer step (one launch per parameter group) matching torch.optim's update
-// formulas (Adam, NAdam with decoupled weight decay, RAdam, SGD) as instantiated by the reference
-// (/root/reference/nkb_classification/utils.py:29-42).  Step-dependent scalars are computed on the
-// host in double precision and passed in; element math is fp32 in torch's operation order.
-// Optionally emits the bf16 shadow copy of the updated parameters in the same pass.
+// formulas (Adam / AdamW, NAdam with decoupled weight decay, RAdam with either decay, SGD with or without momentum) as
+// instantiated by the reference (/root/reference/nkb_classification/utils.py:29-42) and by utils.get_optimizer's optional keys.
+// Step-dependent scalars are computed on the host in double precision and passed in; element math is fp32 in torch's
+// operation order.  Optionally emits the bf16 shadow copy of the updated parameters in the same pass.
 #include "common.h"
 
 struct OptimArgs {
@@ -13,17 +13,33 @@ struct OptimArgs {
     // adam : c0 = lr/bias_correction1, c1 = sqrt(bias_correction2)
     // nadam: c0 = bias_correction2, c1 = lr*(1-mu)/(1-mu_product), c2 = lr*mu_next/(1-mu_product*mu_next)
     // radam: c0 = bias_correction1, c1 = sqrt(bias_correction2), c2 = rect (0 => unrectified branch)
+    // adam / radam: c3 != 0 => decoupled weight decay (AdamW, RAdam(decoupled_weight_decay=True)); nadam ignores c3
+    // sgd  : beta1 = momentum, c0 = factor on the incoming gradient in the buffer update (1 - dampening, or 1 on the step where
+    //        torch clones the gradient into a fresh buffer), c1 != 0 => Nesterov.  beta1 == 0 or c0 == 0 => plain SGD: neither
+    //        moment is touched (callers from before the momentum form hand kind 3 Adam's betas with zeros in c0..c3)
 };
 
+// what a launch reads and writes is uniform per launch, so each form is compiled on its own and the kernels branch once:
+// the Adam family streams both moments, SGD with momentum the first one only, plain SGD no state at all
+enum { OPTIM_ADAM_FAMILY = 0, OPTIM_SGD_PLAIN = 1, OPTIM_SGD_MOMENTUM = 2 };
+__host__ __device__ __forceinline__ int optim_mode(int kind, float beta1, float c0) {
+    return kind != 3 ? OPTIM_ADAM_FAMILY : (beta1 != 0.f && c0 != 0.f ? OPTIM_SGD_MOMENTUM : OPTIM_SGD_PLAIN);
+}
+
 // one element of the update (the arithmetic of torch's single-tensor Adam / NAdam / RAdam / SGD loops, op for op)
+template <int MODE>
 __device__ __forceinline__ void optim_one(float& w, float grad, float& mi, float& vi, const OptimArgs& a) {
     grad = grad * a.grad_scale;
-    if (a.kind == 3) {                                       // SGD, momentum 0
+    if (MODE != OPTIM_ADAM_FAMILY) {                         // SGD
         grad = grad + a.wd * w;
+        if (MODE == OPTIM_SGD_MOMENTUM) {
+            mi = a.beta1 * mi + a.c0 * grad;                 // buf.mul_(momentum).add_(grad, alpha=1-dampening)
+            grad = a.c1 != 0.f ? grad + a.beta1 * mi : mi;   // Nesterov: grad.add(buf, alpha=momentum)
+        }
         w = w - a.lr * grad;
         return;
     }
-    if (a.kind == 1) w = w * (1.f - a.lr * a.wd);            // NAdam: decoupled decay
+    if (a.kind == 1 || a.c3 != 0.f) w = w * (1.f - a.lr * a.wd);   // NAdam, AdamW, RAdam(decoupled): decoupled decay
     else grad = grad + a.wd * w;                             // Adam / RAdam: L2 folded into the gradient
     mi = mi + (grad - mi) * (1.f - a.beta1);                 // exp_avg.lerp_(grad, 1-beta1)
     vi = vi * a.beta2 + (1.f - a.beta2) * grad * grad;
@@ -41,16 +57,15 @@ __device__ __forceinline__ void optim_one(float& w, float grad, float& mi, float
     }
 }
 
-// HBM-bound: 30 bytes per parameter (master weight, both moments read + written, gradient read, bf16 shadow written).  Four
+// HBM-bound: 30 bytes per parameter (master weight, both moments read + written, gradient read, bf16 shadow written); SGD with
+// momentum moves 22 (no second moment), plain SGD 14.  Four
 // parameters per lane per access (16-byte loads / stores on every stream) and two such groups in flight per thread: 5.3 TB/s
 // standalone (scripts/optim_bench.py: 304 M parameters in 1.73 ms); unicom ViT-L/14's 573 M parameters take 3.13 ms in the step
 // (5.5 TB/s) against 3.6 ms for the one-element-per-thread form this replaces.
-__global__ void __launch_bounds__(256) optim_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                         float* __restrict__ v, bf16_t* __restrict__ shadow, size_t n,
-                                                         const OptimArgs a, const float* __restrict__ skip) {
-    // skipped step of the gradient scaler (engine.py:59, GradScaler.step): decided on the device, no host round trip
-    if (skip && *skip != 0.f) return;
-    const bool moments = a.kind != 3;
+template <int MODE>
+__device__ __forceinline__ void optim_step_vec(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                               float* __restrict__ v, bf16_t* __restrict__ shadow, size_t n, const OptimArgs& a) {
+    constexpr bool use_m = MODE != OPTIM_SGD_PLAIN, use_v = MODE == OPTIM_ADAM_FAMILY;
     const size_t n4 = n >> 2, stride = (size_t)gridDim.x * blockDim.x;
     f32x4* p4 = (f32x4*)p; const f32x4* g4 = (const f32x4*)g; f32x4* m4 = (f32x4*)m; f32x4* v4 = (f32x4*)v;
     u32x2* s2 = (u32x2*)shadow;
@@ -60,17 +75,22 @@ __global__ void __launch_bounds__(256) optim_step_kernel(float* __restrict__ p, 
         f32x4 w[2], gr[2], mi[2] = {}, vi[2] = {};
         w[0] = p4[i0]; gr[0] = __builtin_nontemporal_load(g4 + i0);
         if (two) { w[1] = p4[i1]; gr[1] = __builtin_nontemporal_load(g4 + i1); }
-        if (moments) {
-            mi[0] = __builtin_nontemporal_load(m4 + i0); vi[0] = __builtin_nontemporal_load(v4 + i0);
-            if (two) { mi[1] = __builtin_nontemporal_load(m4 + i1); vi[1] = __builtin_nontemporal_load(v4 + i1); }
+        if (use_m) {
+            mi[0] = __builtin_nontemporal_load(m4 + i0);
+            if (use_v) vi[0] = __builtin_nontemporal_load(v4 + i0);
+            if (two) {
+                mi[1] = __builtin_nontemporal_load(m4 + i1);
+                if (use_v) vi[1] = __builtin_nontemporal_load(v4 + i1);
+            }
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
             if (u == 1 && !two) break;
             const size_t i = u ? i1 : i0;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { float w_ = w[u][e], m_ = mi[u][e], v_ = vi[u][e]; optim_one(w_, gr[u][e], m_, v_, a); w[u][e] = w_; mi[u][e] = m_; vi[u][e] = v_; }
-            if (moments) { __builtin_nontemporal_store(mi[u], m4 + i); __builtin_nontemporal_store(vi[u], v4 + i); }
+            for (int e = 0; e < 4; ++e) { float w_ = w[u][e], m_ = mi[u][e], v_ = vi[u][e]; optim_one<MODE>(w_, gr[u][e], m_, v_, a); w[u][e] = w_; mi[u][e] = m_; vi[u][e] = v_; }
+            if (use_m) __builtin_nontemporal_store(mi[u], m4 + i);
+            if (use_v) __builtin_nontemporal_store(vi[u], v4 + i);
             __builtin_nontemporal_store(w[u], p4 + i);
             if (shadow) {
                 u32x2 o;
@@ -82,31 +102,62 @@ __global__ void __launch_bounds__(256) optim_step_kernel(float* __restrict__ p, 
     }
     // (n % 4 tail)
     for (size_t i = (n4 << 2) + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        float w_ = p[i], m_ = moments ? m[i] : 0.f, v_ = moments ? v[i] : 0.f;
-        optim_one(w_, g[i], m_, v_, a);
-        if (moments) { m[i] = m_; v[i] = v_; }
+        float w_ = p[i], m_ = use_m ? m[i] : 0.f, v_ = use_v ? v[i] : 0.f;
+        optim_one<MODE>(w_, g[i], m_, v_, a);
+        if (use_m) m[i] = m_;
+        if (use_v) v[i] = v_;
         p[i] = w_;
         if (shadow) shadow[i] = f2bf(w_);
     }
 }
+__global__ void __launch_bounds__(256) optim_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                         float* __restrict__ v, bf16_t* __restrict__ shadow, size_t n,
+                                                         const OptimArgs a, const float* __restrict__ skip) {
+    // skipped step of the gradient scaler (engine.py:59, GradScaler.step): decided on the device, no host round trip
+    if (skip && *skip != 0.f) return;
+    const int mode = optim_mode(a.kind, a.beta1, a.c0);
+    if (mode == OPTIM_ADAM_FAMILY) optim_step_vec<OPTIM_ADAM_FAMILY>(p, g, m, v, shadow, n, a);
+    else if (mode == OPTIM_SGD_PLAIN) optim_step_vec<OPTIM_SGD_PLAIN>(p, g, m, v, shadow, n, a);
+    else optim_step_vec<OPTIM_SGD_MOMENTUM>(p, g, m, v, shadow, n, a);
+}
 // the same, one parameter per thread: ranges that do not start on a 16-byte boundary
+template <int MODE>
+__device__ __forceinline__ void optim_step_scalar(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                  float* __restrict__ v, bf16_t* __restrict__ shadow, size_t n, const OptimArgs& a) {
+    constexpr bool use_m = MODE != OPTIM_SGD_PLAIN, use_v = MODE == OPTIM_ADAM_FAMILY;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        float w_ = p[i], m_ = use_m ? m[i] : 0.f, v_ = use_v ? v[i] : 0.f;
+        optim_one<MODE>(w_, g[i], m_, v_, a);
+        if (use_m) m[i] = m_;
+        if (use_v) v[i] = v_;
+        p[i] = w_;
+        if (shadow) shadow[i] = f2bf(w_);
+    }
+}
 __global__ void optim_step_scalar_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                          float* __restrict__ v, bf16_t* __restrict__ shadow, size_t n, const OptimArgs a,
                                          const float* __restrict__ skip) {
     if (skip && *skip != 0.f) return;
-    const bool moments = a.kind != 3;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        float w_ = p[i], m_ = moments ? m[i] : 0.f, v_ = moments ? v[i] : 0.f;
-        optim_one(w_, g[i], m_, v_, a);
-        if (moments) { m[i] = m_; v[i] = v_; }
-        p[i] = w_;
-        if (shadow) shadow[i] = f2bf(w_);
-    }
+    const int mode = optim_mode(a.kind, a.beta1, a.c0);
+    if (mode == OPTIM_ADAM_FAMILY) optim_step_scalar<OPTIM_ADAM_FAMILY>(p, g, m, v, shadow, n, a);
+    else if (mode == OPTIM_SGD_PLAIN) optim_step_scalar<OPTIM_SGD_PLAIN>(p, g, m, v, shadow, n, a);
+    else optim_step_scalar<OPTIM_SGD_MOMENTUM>(p, g, m, v, shadow, n, a);
 }
 
 extern "C" int nkb_optim_step(int kind, float* p, const float* g, float* m, float* v, void* shadow_bf16, long long n,
                               float lr, float wd, float beta1, float beta2, float eps, float grad_scale, float c0,
                               float c1, float c2, float c3, const float* skip_flag, hipStream_t stream) {
+    if (kind < 0 || kind > 3) { nkb_set_error("optim_step: kind %d is none of 0 adam, 1 nadam, 2 radam, 3 sgd", kind); return 1; }
+    const int mode = optim_mode(kind, beta1, c0);
+    if (kind == 3 && c1 != 0.f && mode != OPTIM_SGD_MOMENTUM) {
+        nkb_set_error("optim_step: Nesterov SGD (c1 != 0) needs a momentum (beta1 != 0) and c0 != 0");
+        return 1;
+    }
+    if (mode != OPTIM_SGD_PLAIN && !m) {
+        nkb_set_error("optim_step: kind %d with beta1 %g needs the first-moment buffer m", kind, (double)beta1);
+        return 1;
+    }
+    if (kind != 3 && !v) { nkb_set_error("optim_step: kind %d needs the second-moment buffer v", kind); return 1; }
     if (n <= 0) return 0;
     OptimArgs a;
     a.kind = kind; a.lr = lr; a.wd = wd; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps; a.grad_scale = grad_scale;

@@ -22,6 +22,25 @@ class _ParamOnly(nn.Module):
                            "(call the classifier returned by get_model, on a cuda device)")
 
 
+def transformer_layer_groups(backbone: nn.Module) -> List[List[nn.Parameter]]:
+    """Layer ids of a transformer backbone for layer-wise lr decay (utils.get_optimizer, `layer_decay`): entry k lists the
+    parameters of id k in `parameters()` order.  Id 0 holds what sits in front of the blocks (cls_token, pos_embed, patch_embed.*,
+    norm_pre.*), id i + 1 is blocks.i.*, id depth + 1 everything after the blocks (the final norm, unicom's feature head).  The
+    usual fine-tuning rule restated (BEiT / MAE / DINOv2 recipes), not pinned against timm's own grouping."""
+    depth = len(backbone.blocks)
+    groups: List[List[nn.Parameter]] = [[] for _ in range(depth + 2)]
+    for name, p in backbone.named_parameters():
+        head = name.split(".")[0]
+        if head == "blocks":
+            k = int(name.split(".")[1]) + 1
+        elif head in ("cls_token", "pos_embed", "patch_embed", "norm_pre"):
+            k = 0
+        else:
+            k = depth + 1
+        groups[k].append(p)
+    return groups
+
+
 class _Basic(_ParamOnly):
     expansion = 1
 

@@ -24,7 +24,7 @@ import torch
 from torch import nn
 
 from . import hip
-from .backbones import _ParamOnly
+from .backbones import _ParamOnly, transformer_layer_groups
 from .hipnet import HipEngine
 
 
@@ -92,6 +92,10 @@ class HipUnicomViT(_ParamOnly):
                 nn.init.trunc_normal_(m.weight, std=0.02)
                 if m.bias is not None:
                     nn.init.zeros_(m.bias)
+
+    def layer_groups(self):
+        """Parameters per layer id (embeddings, one id per block, what follows the blocks) for `layer_decay`."""
+        return transformer_layer_groups(self)
 
     def gemm_convs(self):
         return [m for m in self.modules() if isinstance(m, nn.Linear)]

@@ -3,7 +3,10 @@
 Drop-in for /root/reference/nkb_classification/utils.py: `get_optimizer` (utils.py:10-42) keeps the two
 parameter groups (backbone / classifier) with per-group lr and weight decay and the same optimizer
 families, but the update itself is one fused HIP launch per group over the model's flat parameter arena
-(nkb_optim_step) instead of torch's foreach kernels.  `get_scheduler` (utils.py:45-61) returns the stock
+(nkb_optim_step) instead of torch's foreach kernels.  Beyond the reference: `type: "adamw"`, the optional keys
+`betas`, `eps`, `momentum`, `dampening`, `nesterov`, `decoupled_weight_decay`, `amsgrad` (refused when true) and
+`layer_decay` (one backbone group per transformer block); a config without them builds what the reference builds.
+`get_scheduler` (utils.py:45-61) returns the stock
 torch schedulers, which only touch `param_groups[i]["lr"]` on the host.
 """
 from __future__ import annotations
@@ -19,23 +22,36 @@ from torch.optim import lr_scheduler
 
 from . import hip
 
-_KIND = {"adam": 0, "nadam": 1, "radam": 2, "sgd": 3}
+_KIND = {"adam": 0, "adamw": 0, "nadam": 1, "radam": 2, "sgd": 3}
+# optional cfg.optimizer keys that reach the optimizer's defaults, and the kinds whose torch class takes them
+_OPTIONS = {"betas": ("adam", "adamw", "nadam", "radam"), "eps": ("adam", "adamw", "nadam", "radam"),
+            "momentum": ("sgd",), "dampening": ("sgd",), "nesterov": ("sgd",),
+            "decoupled_weight_decay": ("adam", "radam"), "amsgrad": ("adam", "adamw")}
 
 
 def _step_scalars(kind: str, state: dict, *, lr: float, beta1: float, beta2: float, eps: float,
-                  momentum_decay: float = 4e-3):
+                  momentum_decay: float = 4e-3, decoupled: bool = False, momentum: float = 0.0, dampening: float = 0.0,
+                  nesterov: bool = False):
     """Advance the per-group step counter and return (kernel kind, (c0, c1, c2, c3)).
 
     The scalars are the step-dependent coefficients of torch.optim's single-tensor formulas, evaluated in
-    double precision on the host exactly as torch does before it hands them to its kernels.
+    double precision on the host exactly as torch does before it hands them to its kernels.  c3 = 1 asks adam / radam for
+    decoupled weight decay (adamw is adam with c3 = 1).  sgd reads `momentum`, never `beta1` (callers hand it Adam's betas);
+    with a momentum the kernel's beta1 is that momentum, c0 the factor on the gradient in the buffer update, c1 Nesterov.
     """
     step = state["step"] = state.get("step", 0) + 1
     if kind == "sgd":
-        return 3, (0.0, 0.0, 0.0, 0.0)
+        if momentum == 0.0:
+            return 3, (0.0, 0.0, 0.0, 0.0)
+        # torch clones the gradient into the buffer on the first step that has a momentum: no dampening there
+        fresh = not state.get("momentum_buffer", False)
+        state["momentum_buffer"] = True
+        return 3, (1.0 if fresh else 1.0 - dampening, 1.0 if nesterov else 0.0, 0.0, 0.0)
+    c3 = 1.0 if (decoupled or kind == "adamw") else 0.0
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
-    if kind == "adam":
-        return 0, (lr / bc1, math.sqrt(bc2), 0.0, 0.0)
+    if kind in ("adam", "adamw"):
+        return 0, (lr / bc1, math.sqrt(bc2), 0.0, c3)
     if kind == "nadam":
         mu = beta1 * (1.0 - 0.5 * (0.96 ** (step * momentum_decay)))
         mu_next = beta1 * (1.0 - 0.5 * (0.96 ** ((step + 1) * momentum_decay)))
@@ -48,30 +64,38 @@ def _step_scalars(kind: str, state: dict, *, lr: float, beta1: float, beta2: flo
         rect = 0.0
         if rho_t > 5.0:
             rect = math.sqrt((rho_t - 4.0) * (rho_t - 2.0) * rho_inf / ((rho_inf - 4.0) * (rho_inf - 2.0) * rho_t))
-        return 2, (bc1, math.sqrt(bc2), rect, 0.0)
+        return 2, (bc1, math.sqrt(bc2), rect, c3)
     raise NotImplementedError(kind)
 
 
 class FusedOptimizer(torch.optim.Optimizer):
-    """Adam / NAdam(decoupled) / RAdam / SGD with torch's defaults; the math runs in nkb_optim_step.
+    """Adam / AdamW / NAdam(decoupled) / RAdam / SGD (momentum, dampening, Nesterov) with the defaults of the torch class
+    of the same name; the math runs in nkb_optim_step.  `options` override those defaults the way the torch constructors'
+    keyword arguments do, with torch's validation; like every other hyper-parameter they are read from the group at each
+    step, so schedulers that cycle `momentum` or `betas` work.  amsgrad is refused: it needs a third state buffer.
 
     When every parameter of a group is a view into the model's flat arena (see model.ParamArena) the group is
     updated by ONE launch over the contiguous range, which also refreshes the bf16 shadow weights; otherwise
     each parameter gets its own launch.  `grad_scale` (e.g. 1/world_size) is folded into the kernel.
     """
 
-    def __init__(self, params, kind: str, arena=None):
+    def __init__(self, params, kind: str, arena=None, **options):
         self.kind = kind
         # hyper-parameter keys and defaults of the torch optimizer the reference instantiates (utils.py:29-39)
         if kind == "sgd":
             defaults = dict(lr=1e-3, weight_decay=0.0, momentum=0, dampening=0, nesterov=False, maximize=False)
         else:
-            defaults = dict(lr=1e-3, weight_decay=0.0, betas=(0.9, 0.999), eps=1e-8, maximize=False,
-                            decoupled_weight_decay=(kind == "nadam"))
+            defaults = dict(lr=1e-3, weight_decay=1e-2 if kind == "adamw" else 0.0, betas=(0.9, 0.999), eps=1e-8,
+                            maximize=False, decoupled_weight_decay=kind in ("nadam", "adamw"))
             if kind == "nadam":
                 defaults["momentum_decay"] = 4e-3
-            if kind == "adam":
+            if kind in ("adam", "adamw"):
                 defaults["amsgrad"] = False
+        for k, val in options.items():
+            if kind not in _OPTIONS.get(k, ()):
+                raise TypeError(f"optimizer '{kind}' got an unexpected option '{k}'")
+            defaults[k] = tuple(val) if k == "betas" else val
+        _validate(kind, defaults)
         super().__init__(params, defaults)
         self.arena = arena
         self.grad_scale = 1.0
@@ -126,18 +150,26 @@ class FusedOptimizer(torch.optim.Optimizer):
             live = [p for p in group["params"] if p.grad is not None]
             if not live:
                 continue
-            beta1, beta2 = group.get("betas", (0.0, 0.0))
+            _validate(self.kind, group)                       # (a scheduler or the user may have rewritten the group)
+            sgd = self.kind == "sgd"
+            beta1, beta2 = (float(group["momentum"]), 0.0) if sgd else group.get("betas", (0.0, 0.0))
+            dampening = float(group["dampening"]) if sgd else 0.0
             eps = group.get("eps", 0.0)
             lr, wd = float(group["lr"]), float(group["weight_decay"])
             kcode, sc = _step_scalars(self.kind, gstate, lr=lr, beta1=beta1, beta2=beta2, eps=eps,
-                                      momentum_decay=group.get("momentum_decay", 4e-3))
+                                      momentum_decay=group.get("momentum_decay", 4e-3),
+                                      decoupled=bool(group.get("decoupled_weight_decay", False)),
+                                      momentum=beta1 if sgd else 0.0, dampening=dampening,
+                                      nesterov=bool(group.get("nesterov", False)))
+            momentum = sgd and beta1 != 0.0
             rng = self._arena_range(group)
             if rng is not None:
                 lo, hi = rng
                 a = self.arena
                 m, v = a.moments()
                 shadow = a.shadow[lo:hi] if a.shadow is not None else None
-                hip.optim_step(kcode, a.flat_param[lo:hi], a.flat_grad[lo:hi], m[lo:hi], v[lo:hi], shadow, hi - lo,
+                # (SGD with momentum keeps its buffer in the first moment and never reads the second)
+                hip.optim_step(kcode, a.flat_param[lo:hi], a.flat_grad[lo:hi], m[lo:hi], None if momentum else v[lo:hi], shadow, hi - lo,
                                lr, wd, beta1, beta2, eps, self.grad_scale, *sc, skip_flag=skip_flag)
                 touched_arena = True
                 if shadow is not None and len(live) == len(group["params"]):
@@ -146,16 +178,22 @@ class FusedOptimizer(torch.optim.Optimizer):
             for p in live:
                 hip.require_device(p, "optimizer.step")
                 st = self.state[p]
-                if "exp_avg" not in st and self.kind != "sgd":
+                if "exp_avg" not in st and not sgd:
                     st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
                     st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                psc = sc
+                if momentum:                             # "first step" is this parameter's own: torch clones the gradient then
+                    fresh = "momentum_buffer" not in st
+                    if fresh:
+                        st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    psc = (1.0 if fresh else 1.0 - dampening,) + tuple(sc[1:])
                 g = p.grad
                 if g.dtype != torch.float32 or p.dtype != torch.float32:
                     raise RuntimeError("FusedOptimizer: parameters and gradients must be fp32")
                 if not (_dense(p) and _dense(g) and p.stride() == g.stride()):
                     raise RuntimeError("FusedOptimizer: parameter/gradient must be dense with equal strides")
-                hip.optim_step(kcode, p, g, st.get("exp_avg"), st.get("exp_avg_sq"), None, p.numel(), lr, wd, beta1,
-                               beta2, eps, self.grad_scale, *sc, skip_flag=skip_flag)
+                hip.optim_step(kcode, p, g, st.get("momentum_buffer") if sgd else st.get("exp_avg"), st.get("exp_avg_sq"), None,
+                               p.numel(), lr, wd, beta1, beta2, eps, self.grad_scale, *psc, skip_flag=skip_flag)
                 if self.arena is not None and self.arena.owns(p):
                     touched_arena = True
         if touched_arena:
@@ -167,29 +205,75 @@ class FusedOptimizer(torch.optim.Optimizer):
         return loss
 
 
+def _validate(kind: str, group: dict):
+    """torch's constructor checks for the hyper-parameters nkb_optim_step reads, in torch's wording."""
+    if group["lr"] < 0.0:
+        raise ValueError(f"Invalid learning rate: {group['lr']}")
+    if group["weight_decay"] < 0.0:
+        raise ValueError(f"Invalid weight_decay value: {group['weight_decay']}")
+    if kind == "sgd":
+        if group["momentum"] < 0.0:
+            raise ValueError(f"Invalid momentum value: {group['momentum']}")
+        if group["nesterov"] and (group["momentum"] <= 0 or group["dampening"] != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if group["momentum"] != 0 and group["dampening"] == 1:
+            # nkb_optim_step reads a zero factor on the gradient (c0 = 1 - dampening) as plain SGD
+            raise NotImplementedError("dampening=1 with a momentum is not implemented: no gradient would ever enter the buffer "
+                                      "after the first step")
+        return
+    if group["eps"] < 0.0:
+        raise ValueError(f"Invalid epsilon value: {group['eps']}")
+    for i, b in enumerate(group["betas"]):
+        if not 0.0 <= b < 1.0:
+            raise ValueError(f"Invalid beta parameter at index {i}: {b}")
+    if group.get("amsgrad", False):
+        raise NotImplementedError("amsgrad=True is not implemented: it needs a third state buffer, and nkb_optim_step "
+                                  "has no pointer for one")
+    if kind == "nadam" and not group.get("decoupled_weight_decay", True):
+        raise NotImplementedError("nadam runs with decoupled weight decay only, as the reference builds it")
+
+
 def _dense(t: torch.Tensor) -> bool:
     return t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last) or \
         t.numel() == t.untyped_storage().nbytes() // t.element_size()
 
 
+def _backbone_groups(model, layer_decay, lr, wd):
+    """Layer-wise lr decay, the usual ViT fine-tuning rule (BEiT / MAE / DINOv2 recipes; restated, not pinned against timm, which
+    is not a dependency): the backbone's layer ids come from its `layer_groups()` (id 0 the embeddings, i + 1 block i, depth + 1
+    what follows the blocks); id k of `top = depth + 1` trains at `lr * layer_decay ** (top - k)`.  One group per id that has
+    parameters, in id order: each is one contiguous arena range, so it still costs one launch."""
+    d = float(layer_decay)
+    if not 0.0 < d <= 1.0:
+        raise ValueError(f"layer_decay must lie in (0, 1], got {layer_decay}")
+    layer_groups = getattr(model.emb_model, "layer_groups", None)
+    if layer_groups is None:
+        raise NotImplementedError(f"layer_decay is implemented for the ViT families only (timm-style ViT, unicom ViT), "
+                                  f"not for {type(model.emb_model).__name__}")
+    per_id = layer_groups()
+    top = len(per_id) - 1
+    return [{"params": ps, "lr": lr * d ** (top - k), "weight_decay": wd} for k, ps in enumerate(per_id) if ps]
+
+
 def get_optimizer(model, cfg_optimizer):
     lr = cfg_optimizer.get("lr", 0.001)
     wd = cfg_optimizer.get("weight_decay", 0.0)
-    groups = [
-        {"params": list(model.emb_model.parameters()),
-         "lr": cfg_optimizer.get("backbone_lr", lr),
-         "weight_decay": cfg_optimizer.get("backbone_weight_decay", wd)},
-        {"params": list(model.classifier.parameters()),
-         "lr": cfg_optimizer.get("classifier_lr", lr),
-         "weight_decay": cfg_optimizer.get("classifier_weight_decay", wd)},
-    ]
+    backbone_lr, backbone_wd = cfg_optimizer.get("backbone_lr", lr), cfg_optimizer.get("backbone_weight_decay", wd)
+    if cfg_optimizer.get("layer_decay") is not None:
+        groups = _backbone_groups(model, cfg_optimizer["layer_decay"], backbone_lr, backbone_wd)
+    else:
+        groups = [{"params": list(model.emb_model.parameters()), "lr": backbone_lr, "weight_decay": backbone_wd}]
+    groups.append({"params": list(model.classifier.parameters()),
+                   "lr": cfg_optimizer.get("classifier_lr", lr),
+                   "weight_decay": cfg_optimizer.get("classifier_weight_decay", wd)})
     kind = cfg_optimizer["type"].lower()
     if kind == "sparse_adam":
         # utils.py:36 builds torch's SparseAdam; it needs sparse gradients, which no model of this package produces.
         return torch.optim.SparseAdam(groups)
     if kind not in _KIND:
         raise NotImplementedError(f'Unknown optimizer in config: {cfg_optimizer["type"]}')
-    return FusedOptimizer(groups, kind, arena=getattr(model, "arena", None))
+    options = {k: cfg_optimizer[k] for k in _OPTIONS if k in cfg_optimizer}
+    return FusedOptimizer(groups, kind, arena=getattr(model, "arena", None), **options)
 
 
 def get_scheduler(opt, lr_policy):

@@ -17,7 +17,7 @@ import torch
 from torch import nn
 
 from . import hip
-from .backbones import _ParamOnly
+from .backbones import _ParamOnly, transformer_layer_groups
 from .hipnet import HipEngine
 
 
@@ -90,6 +90,10 @@ class HipViT(_ParamOnly):
             if isinstance(m, nn.Linear):
                 nn.init.trunc_normal_(m.weight, std=0.02)
                 nn.init.zeros_(m.bias)
+
+    def layer_groups(self):
+        """Parameters per layer id (embeddings, one id per block, what follows the blocks) for `layer_decay`."""
+        return transformer_layer_groups(self)
 
     def gemm_convs(self):
         return [m for m in self.modules() if isinstance(m, nn.Linear)]
