@@ -73,6 +73,10 @@ int nkb_conv_gemm(int dtype, int mode, const void* x, const void* w, void* y, co
 /* add_bits (optional): ReLU bit mask of the `add` operand as written by nkb_bn_apply(relu_bits): add[m][c] only counts
  * where its bit is set (the gradient of a residual block's output, masked on the fly instead of in a separate pass). */
 int nkb_conv_gemm_stat_tiles(int dtype, int M, int Cout);
+/* Which conv_igemm_kernel<T, TC, TP, BNB, HALO> instance the last launch of this family took (tests prove with it that every
+ * compiled instance is reached): bit 0 bf16, bit 1 the 64 x 256 tile, bit 2 HALO, bit 3 grouped tile walk, bits 4.. the epilogue
+ * selector BNB.  -1 before any launch.  One host-side store per launch; launches that go to another core leave it alone. */
+int nkb_conv_last_instance(void);
 
 /* Weight gradient: dw[co][r][s][ci] += sum_{n,p,q} dy[n,p,q,co] * x[n, p*stride+r-pad, q*stride+s-pad, ci] (fp32 atomics);
  * optional bias gradient dbias[co] += sum_{n,p,q} dy[n,p,q,co] from the same pass over dy. */

@@ -1208,6 +1208,7 @@ int nkb_launch_wgrad_reduce2(const float* part, long long slab, int splits, floa
 
 // ------------------------------------------------------------------------------------------
 // host launchers
+static int g_conv_last_instance = -1;   // nkb_conv_last_instance: the instance launch_conv_impl launched last
 template <typename T, int TC, int TP, int BNB, bool HALO>
 static int launch_conv_impl(ConvParams& p, hipStream_t stream, int batch) {
     p.tilesM = (p.M + TP - 1) / TP;
@@ -1233,9 +1234,11 @@ static int launch_conv_impl(ConvParams& p, hipStream_t stream, int batch) {
         attr_set = true;
     }
     const unsigned grid = (unsigned)p.tilesM * (unsigned)p.tilesN;
+    g_conv_last_instance = (int)(sizeof(T) == 2) | (int)(TC == 64) << 1 | (int)HALO << 2 | (int)(p.group_m > 1) << 3 | BNB << 4;
     hipLaunchKernelGGL((conv_igemm_kernel<T, TC, TP, BNB, HALO>), dim3(grid, batch), dim3(256), lds, stream, p);
     return nkb_check_launch("conv_igemm");
 }
+extern "C" int nkb_conv_last_instance(void) { return g_conv_last_instance; }
 
 // whether a bf16 launch that asks for epilogue BNB can take that epilogue's lean instantiation
 template <int BNB>

@@ -371,6 +371,12 @@ def stat_tiles(dtype, M, Cout):
     return load().nkb_conv_gemm_stat_tiles(dtype, M, Cout)
 
 
+def conv_last_instance() -> int:
+    """The conv_igemm_kernel instance of the last launch of that family (bit 0 bf16, bit 1 the 64 x 256 tile, bit 2 HALO, bit 3
+    grouped walk, bits 4.. the epilogue selector); -1 before any launch."""
+    return int(load().nkb_conv_last_instance())
+
+
 def convp_tiles(dtype, kind, *, N, H, W, Cin, ldx, Cout, ldy, R, S, stride, pad) -> int:
     """Partial-sum rows of the row-balanced 3x3 core for this launch (kind 0 forward, 1 data gradient); 0 = not eligible."""
     return int(load().nkb_convp_tiles(dtype, kind, N, H, W, Cin, ldx, Cout, ldy, R, S, stride, pad))
