@@ -368,8 +368,17 @@ int nkb_attn_softmax(int dtype, int backward, const float* s, int lds, const voi
                      long long rows, int cols, float scale, nkb_stream_t stream);
 /* Fused attention (bf16, head dim 64, T <= 256): O = softmax(QK^T*scale)V with per-row log-sum-exp; the backward half
  * recomputes P from Q, K, LSE and writes P and dS = P o (dP - rowsum(P o dP)) * scale as [B*H][T][ldp] bf16. */
+/* Attention dropout (timm Attention.attn_drop), drop_p in [0, 1); drop_p == 0 ignores seed, drop_ld and the seed buffer.
+ * With P = softmax(QK^T*scale), c = 1/(1-drop_p): O = (P o keep * c) V, lse stays that of the undropped scores; backward
+ * dP = (dO V^T) o keep * c, dS = P o (dP - rowsum(P o dP)) * scale, dV = (P o keep * c)^T dO.  keep(b, h, q, k) is, bit for bit,
+ * the mask byte nkb_dropout(seed, drop_p) writes for element ((b*H + h)*T + q) * drop_ld + k of a [B*H][T][drop_ld] tensor
+ * (drop_ld >= T: a row pitch of the index only, nothing of that size is read or written); the kernels recompute it, no mask is
+ * stored.  The forward pass leaves `seed` in *seed_out (8 bytes of device memory); the backward pass, a launch of its own that may
+ * be replayed from a plan, reads it back from seed_dev.  Refused before any launch: drop_p outside [0, 1), and with drop_p > 0 a
+ * drop_ld < T or a missing seed_out / seed_dev. */
 int nkb_attn_forward(int dtype, const void* qkv, void* out, float* lse, int B, int T, int H, int dh, float scale,
-                     void* outq, float* q_state, nkb_stream_t stream);
+                     void* outq, float* q_state, float drop_p, unsigned long long seed, int drop_ld, long long* seed_out,
+                     nkb_stream_t stream);
 /* dq != NULL: the same pass also forms dQ = dS K and stores it at dq[(b*T + q) * ld_dq + h*64 ..] (e.g. the Q third of the
  * d_qkv matrix, ld_dq = 3*H*64), so that only dV = P^T dO and dK = dS^T Q remain as separate GEMMs. */
 int nkb_attn_backward_ds(int dtype, const void* qkv, const void* dout, const float* lse, void* P, void* dS, int ldp, int B,
@@ -380,7 +389,8 @@ int nkb_attn_backward_ds(int dtype, const void* qkv, const void* dout, const flo
 /* (colsum / colsum_work, optional: colsum[3 H dh] += the column sums of the stored d_qkv rows = the qkv projection's bias gradient,
  * from per-image sums in colsum_work[B][3 H dh] added in image order — no separate pass over d_qkv) */
 int nkb_attn_backward(int dtype, const void* qkv, const void* dout, const void* out, const float* lse, void* dqkv, int B, int T,
-                      int H, int dh, float scale, void* dqkv_q, float* q_state, float* colsum, float* colsum_work, nkb_stream_t stream);
+                      int H, int dh, float scale, void* dqkv_q, float* q_state, float* colsum, float* colsum_work, float drop_p,
+                      const long long* seed_dev, int drop_ld, nkb_stream_t stream);
 /* (outq / dqkv_q with q_state, optional: fp8 copies of the outputs — e4m3 of `out`, e5m2 of `dqkv`, packed rows, scale q_state[0],
  * amax into q_state[2] as nkb_fp8_quantize would — for the fp8 projection / qkv-gradient GEMMs that consume them.) */
 int nkb_head_transpose(int dtype, const void* in, int ld_in, long long sio, long long sii, int outer, int inner, void* out,

@@ -35,6 +35,12 @@ namespace {
 #ifndef NKB_ATTN_BWD_THREADS
 #define NKB_ATTN_BWD_THREADS 1024
 #endif
+// The DROP flavour of the forward kernel (attention dropout, below) carries the row's index words and the hash temporaries on top of the
+// score row; it has launch bounds of its own, apart from the p = 0 instances above.  With 4 it fits 128 VGPRs with 2 (14 key blocks) and 4
+// (16 key blocks) spilled registers and none elsewhere; with 2 those two instances take 130 / 134 VGPRs: one workgroup per CU.
+#ifndef NKB_ATTN_FWD_DROP_WAVES
+#define NKB_ATTN_FWD_DROP_WAVES 4
+#endif
 
 constexpr int MAXKB = 16;                    // 16-key blocks per row (T <= 256)
 constexpr int DH = 64;
@@ -82,6 +88,31 @@ __device__ __forceinline__ void score_tile(const unsigned char* rows_img, const 
     }
 }
 
+// Attention dropout (the DROP flavour of the forward and the fused backward kernel): Pd = P o keep / (1 - p) takes P's place in O = Pd V
+// and dV = Pd^T dO, and dP = (dO V^T) o keep / (1 - p).  keep(b, h, q, k) is nkb_dropout's decision (common.h: dropout_keep) for element
+// ((b H + h) T + q) * ld + k of a [B*H][T][ld] tensor under the same seed, recomputed for the elements a lane holds: no mask, P or Pd
+// reaches memory.  The forward kernel leaves the seed it used in device memory (seed_out), the backward kernel reads it from there
+// (seed_dev).  The kernels without DROP ignore the whole struct.
+struct AttnDrop {
+    unsigned thresh;                 // dropout_thresh(p)
+    float c;                         // 1 / (1 - p)
+    unsigned long long seed;         // forward
+    long long* seed_out;             // forward: *seed_out = seed
+    const long long* seed_dev;       // backward
+    int ld;
+};
+// keep decisions along one score row (element indices base .. base + 255, base = the row's first index): the low index word is one
+// add per element, and the high word's share of the hash is one of two values prepared per row (a carry out of the low word)
+struct DropRow {
+    unsigned lo, h0, h1;
+    __device__ __forceinline__ DropRow(unsigned long long base, unsigned seed_hi)
+        : lo((unsigned)base), h0(dropout_hi_term((unsigned)(base >> 32), seed_hi)), h1(dropout_hi_term((unsigned)(base >> 32) + 1u, seed_hi)) {}
+    __device__ __forceinline__ bool keep(int k, unsigned seed_lo, unsigned thresh) const {
+        const unsigned il = lo + (unsigned)k;
+        return dropout_hash(il, il < lo ? h1 : h0, seed_lo) >= thresh;
+    }
+};
+
 __device__ __forceinline__ float group_sum(float v) { v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64); return v; }
 __device__ __forceinline__ float group_max(float v) { v = fmaxf(v, __shfl_xor(v, 16, 64)); v = fmaxf(v, __shfl_xor(v, 32, 64)); return v; }
 
@@ -118,10 +149,11 @@ __device__ __forceinline__ void publish_amax(attn_u16x2 amax2, float* q_state) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-template <int NKB, int WPS>
+template <int NKB, int WPS, bool DROP>
 __global__ __launch_bounds__(512, WPS) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                           float* __restrict__ lse, int T, int H, float scale,
-                                                          unsigned char* __restrict__ outq, float* __restrict__ q_state) {
+                                                          unsigned char* __restrict__ outq, float* __restrict__ q_state,
+                                                          const AttnDrop drop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int TK = NKB * 16, NKS = (NKB + 1) / 2;   // 32-key steps of the P*V product
     const int D = H * DH;
@@ -143,6 +175,9 @@ __global__ __launch_bounds__(512, WPS) void attn_fwd_kernel(const bf16_t* __rest
     const float sl2 = scale * 1.4426950408889634f;   // exp(x) = exp2(x log2 e): the hardware exponential is base 2
     const float qscale = outq ? q_state[0] : 1.f;
     attn_u16x2 amax2 = {0, 0};
+    if constexpr (DROP) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) *drop.seed_out = (long long)drop.seed;     // for the backward pass
+    }
     for (int qb = lwave; qb * 16 < T; qb += 8) {           // 8 waves per workgroup, 2 workgroups per CU: 4 waves per SIMD
         const int q = qb * 16 + fr;
         f32x4 acc[NKB];
@@ -184,12 +219,27 @@ __global__ __launch_bounds__(512, WPS) void attn_fwd_kernel(const bf16_t* __rest
         // so the swizzled offsets are lane constants per i and a step is +4096 B.  P is packed to bf16 two key blocks at a
         // time, right before the step that consumes it (a whole-row packed copy cost 32 more live registers).
         const int vr = 4 * g + (fr >> 2), pc = fr & 3;
+        const DropRow row(DROP ? (((unsigned long long)b * H + h) * T + q) * (unsigned long long)drop.ld : 0ull, (unsigned)(drop.seed >> 32));
+        const float invc = inv * drop.c;
 #pragma unroll
         for (int t = 0; t < NKS; ++t) {
-            u32x4 pb = {pack_bf2(acc[2 * t][0] * inv, acc[2 * t][1] * inv), pack_bf2(acc[2 * t][2] * inv, acc[2 * t][3] * inv), 0u, 0u};
-            if (2 * t + 1 < NKB) {
-                pb[2] = pack_bf2(acc[2 * t + 1][0] * inv, acc[2 * t + 1][1] * inv);
-                pb[3] = pack_bf2(acc[2 * t + 1][2] * inv, acc[2 * t + 1][3] * inv);
+            u32x4 pb;
+            if constexpr (DROP) {
+                // Pd = P o keep / (1 - p), this lane's 8 keys of the step; lse and the row sum above are those of the undropped scores
+                float pd[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int kb = 2 * t + (j >> 2), e = j & 3;
+                    pd[j] = 0.f;
+                    if (kb < NKB) pd[j] = row.keep(16 * kb + 4 * g + e, (unsigned)drop.seed, drop.thresh) ? acc[kb][e] * invc : 0.f;
+                }
+                pb = (u32x4){pack_bf2(pd[0], pd[1]), pack_bf2(pd[2], pd[3]), pack_bf2(pd[4], pd[5]), pack_bf2(pd[6], pd[7])};
+            } else {
+                pb = (u32x4){pack_bf2(acc[2 * t][0] * inv, acc[2 * t][1] * inv), pack_bf2(acc[2 * t][2] * inv, acc[2 * t][3] * inv), 0u, 0u};
+                if (2 * t + 1 < NKB) {
+                    pb[2] = pack_bf2(acc[2 * t + 1][0] * inv, acc[2 * t + 1][1] * inv);
+                    pb[3] = pack_bf2(acc[2 * t + 1][2] * inv, acc[2 * t + 1][3] * inv);
+                }
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -331,11 +381,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_ds_kernel(const bf16_t* __res
 //             operands of dV^T += dO^T P and dK^T += Q^T dS, with dO^T / Q^T read through the transposing LDS read in the
 //             matching query permutation.
 // The passes need no barrier between them (delta comes from the prologue), so the waves drift through both independently.
-template <int NKB>
+// DROP (attention dropout, see AttnDrop): dP = (dO V^T) o keep / (1 - p) in both passes, and pass B forms dV from Pd = P o keep / (1 - p);
+// delta = rowsum(P o dP) still equals rowsum(dO o O) because O = Pd V, so the prologue is the same.
+template <int NKB, bool DROP>
 __global__ __launch_bounds__(NKB_ATTN_BWD_THREADS, 1) void attn_bwd_fused_kernel(
     const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout, const bf16_t* __restrict__ out,
     const float* __restrict__ lse, bf16_t* __restrict__ dqkv, int T, int H, float scale,
-    unsigned char* __restrict__ dqkv_q, float* __restrict__ q_state, float* __restrict__ colpart) {
+    unsigned char* __restrict__ dqkv_q, float* __restrict__ q_state, float* __restrict__ colpart, const AttnDrop drop) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int NKS = (NKB + 1) / 2, ROWS = NKS * 32, IMG = ROWS * 128;
     ATTN_STAMP(0);
@@ -411,6 +463,12 @@ __global__ __launch_bounds__(NKB_ATTN_BWD_THREADS, 1) void attn_bwd_fused_kernel
     ATTN_STAMP(1);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, g = lane >> 4;
     const float sl2 = scale * 1.4426950408889634f;
+    unsigned seed_lo = 0u, seed_hi = 0u;
+    if constexpr (DROP) {
+        const unsigned long long seed = (unsigned long long)*drop.seed_dev;        // what the forward pass drew its mask from
+        seed_lo = (unsigned)seed; seed_hi = (unsigned)(seed >> 32);
+    }
+    const unsigned long long drop_base = ((unsigned long long)b * H + h) * T * (unsigned long long)drop.ld;    // index of P[b][h][0][0]
     const int o0 = swz128(fr, g), o1 = swz128(fr, 4 + g);      // fragment offsets of row fr; +2048 per 16-row block
     const int vr = 4 * g + (fr >> 2), pc = fr & 3;
     // transposed fragment for dh block i of 32-row step t (rows vr and vr + 16 of the step)
@@ -475,6 +533,7 @@ __global__ __launch_bounds__(NKB_ATTN_BWD_THREADS, 1) void attn_bwd_fused_kernel
         const bf16x8 q0 = *(const bf16x8*)(Qs + 2048 * qb + o0), q1 = *(const bf16x8*)(Qs + 2048 * qb + o1);
         const bf16x8 d0 = *(const bf16x8*)(Ds + 2048 * qb + o0), d1 = *(const bf16x8*)(Ds + 2048 * qb + o1);
         const float l2 = l2s[q], delta = dls[q];
+        const DropRow row(DROP ? drop_base + (unsigned long long)q * drop.ld : 0ull, seed_hi);
         f32x4 o[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) o[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -500,6 +559,10 @@ __global__ __launch_bounds__(NKB_ATTN_BWD_THREADS, 1) void attn_bwd_fused_kernel
 #pragma unroll
                     for (int e = 0; e < 4; ++e) pe[e] = kb * 16 + 4 * g + e >= T ? 0.f : pe[e];
                 }
+                if constexpr (DROP) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) dp[e] = row.keep(kb * 16 + 4 * g + e, seed_lo, drop.thresh) ? dp[e] * drop.c : 0.f;
+                }
 #pragma unroll
                 for (int e = 0; e < 4; ++e) d[e] = pe[e] * (dp[e] - delta);
                 pd[hb] = (u32x2){pack_bf2(d[0], d[1]), pack_bf2(d[2], d[3])};
@@ -523,6 +586,8 @@ __global__ __launch_bounds__(NKB_ATTN_BWD_THREADS, 1) void attn_bwd_fused_kernel
     for (int kb = (wave + NW - 1) % NW; kb < NKB; kb += NW) {
         const bf16x8 kf0 = *(const bf16x8*)(Ks + 2048 * kb + o0), kf1 = *(const bf16x8*)(Ks + 2048 * kb + o1);
         const bf16x8 vf0 = *(const bf16x8*)(Vs + 2048 * kb + o0), vf1 = *(const bf16x8*)(Vs + 2048 * kb + o1);
+        // (DROP: this lane's key column, at the first of its four queries of a block; query qb * 16 + 4 g + e is (qb * 16 + e) * ld further)
+        const unsigned long long drop_col = drop_base + (unsigned long long)(4 * g) * drop.ld + (unsigned)(kb * 16 + fr);
         f32x4 ov[4], ok[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) { ov[i] = (f32x4){0.f, 0.f, 0.f, 0.f}; ok[i] = (f32x4){0.f, 0.f, 0.f, 0.f}; }
@@ -544,7 +609,13 @@ __global__ __launch_bounds__(NKB_ATTN_BWD_THREADS, 1) void attn_bwd_fused_kernel
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     pv[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(S[e], sl2, -l4[e]));
-                    dv[e] = pv[e] * (dP[e] - d4[e]);     // dS / scale: the factor goes on the finished dK block
+                    if constexpr (DROP) {
+                        const bool keep = dropout_keep(drop_col + (unsigned long long)(qb * 16 + e) * drop.ld, seed_lo, seed_hi, drop.thresh);
+                        dv[e] = pv[e] * ((keep ? dP[e] * drop.c : 0.f) - d4[e]);
+                        pv[e] = keep ? pv[e] * drop.c : 0.f;     // Pd, the operand of dV
+                    } else {
+                        dv[e] = pv[e] * (dP[e] - d4[e]);     // dS / scale: the factor goes on the finished dK block
+                    }
                 }
                 pkp[hb] = (u32x2){pack_bf2(pv[0], pv[1]), pack_bf2(pv[2], pv[3])};
                 pks[hb] = (u32x2){pack_bf2(dv[0], dv[1]), pack_bf2(dv[2], dv[3])};
@@ -583,24 +654,38 @@ __global__ __launch_bounds__(NKB_ATTN_BWD_THREADS, 1) void attn_bwd_fused_kernel
 
 }  // namespace
 
+// the dropout arguments of the two entry points, checked on the host before any launch; seed_buf: seed_out (forward) / seed_dev (backward)
+static int attn_drop_args_ok(const char* who, const char* seed_name, float drop_p, int drop_ld, const void* seed_buf, int T) {
+    if (!(drop_p >= 0.f && drop_p < 1.f)) { nkb_set_error("%s: drop_p=%f outside [0,1)", who, drop_p); return 0; }
+    if (drop_p == 0.f) return 1;
+    if (drop_ld < T) { nkb_set_error("%s: drop_ld=%d is below T=%d (the row pitch of the mask's element index)", who, drop_ld, T); return 0; }
+    if (!seed_buf) { nkb_set_error("%s: drop_p > 0 needs %s (8 bytes of device memory for the seed)", who, seed_name); return 0; }
+    return 1;
+}
+
 // outq / q_state (optional): e4m3 copy of out ([B*T][H*dh] bytes; scale q_state[0], amax into q_state[2]) for an fp8 projection
+// drop_p > 0: attention dropout with nkb_dropout's mask for a [B*H][T][drop_ld] tensor under `seed`; the seed is left in *seed_out
 extern "C" int nkb_attn_forward(int dtype, const void* qkv, void* out, float* lse, int B, int T, int H, int dh, float scale,
-                                void* outq, float* q_state, hipStream_t stream) {
+                                void* outq, float* q_state, float drop_p, unsigned long long seed, int drop_ld, long long* seed_out,
+                                hipStream_t stream) {
     if (outq && !q_state) { nkb_set_error("attn_forward: the fp8 output needs its scaling state"); return 1; }
     if (dtype != NKB_DT_BF16 || dh != DH || T > 16 * MAXKB || T < 1) {
         nkb_set_error("attn_forward: fused path needs bf16, head dim 64, T <= 256 (got dtype %d, dh %d, T %d)", dtype, dh, T);
         return 1;
     }
+    if (!attn_drop_args_ok("attn_forward", "seed_out", drop_p, drop_ld, seed_out, T)) return 1;
+    const bool dropping = drop_p > 0.f;
+    const AttnDrop drop = {dropout_thresh(drop_p), 1.f / (1.f - drop_p), seed, seed_out, nullptr, drop_ld};
     const int nkb = (T + 15) / 16, nks = (T + 31) / 32;
     const int lds = nkb * 16 * 128 + nks * 32 * 128;
     NkbProfScope prof(NKB_K_ATTN, stream, 4.0 * B * H * (double)T * T * DH);
-#define NKB_ATTN_FWD1(N, W)                                                                                                  \
+#define NKB_ATTN_FWD1(N, W, DR)                                                                                              \
     {                                                                                                                        \
         static bool attr = false;                                                                                            \
-        if (!attr) { hipFuncSetAttribute((const void*)attn_fwd_kernel<N, W>, hipFuncAttributeMaxDynamicSharedMemorySize, 68 * 1024); attr = true; } \
-        hipLaunchKernelGGL((attn_fwd_kernel<N, W>), dim3(B * H), dim3(512), lds, stream, (const bf16_t*)qkv, (bf16_t*)out, lse, T, H, scale, (unsigned char*)outq, q_state); \
+        if (!attr) { hipFuncSetAttribute((const void*)attn_fwd_kernel<N, W, DR>, hipFuncAttributeMaxDynamicSharedMemorySize, 68 * 1024); attr = true; } \
+        hipLaunchKernelGGL((attn_fwd_kernel<N, W, DR>), dim3(B * H), dim3(512), lds, stream, (const bf16_t*)qkv, (bf16_t*)out, lse, T, H, scale, (unsigned char*)outq, q_state, drop); \
     }
-#define NKB_ATTN_FWD(N) case N: if (waves == 2) NKB_ATTN_FWD1(N, 2) else NKB_ATTN_FWD1(N, 4) break;
+#define NKB_ATTN_FWD(N) case N: if (dropping) NKB_ATTN_FWD1(N, NKB_ATTN_FWD_DROP_WAVES, true) else if (waves == 2) NKB_ATTN_FWD1(N, 2, false) else NKB_ATTN_FWD1(N, 4, false) break;
     constexpr int waves = NKB_ATTN_FWD_WAVES;
     switch (nkb) {
         NKB_ATTN_FWD(1) NKB_ATTN_FWD(2) NKB_ATTN_FWD(3) NKB_ATTN_FWD(4) NKB_ATTN_FWD(5) NKB_ATTN_FWD(6) NKB_ATTN_FWD(7) NKB_ATTN_FWD(8)
@@ -641,31 +726,36 @@ extern "C" int nkb_attn_backward_ds(int dtype, const void* qkv, const void* dout
 // dqkv_q / q_state (optional): e5m2 copy of dqkv ([B*T][3*H*dh] bytes) for the fp8 data / weight gradient of the qkv projection
 // colsum / colsum_work (optional): colsum[3 H dh] += the column sums of the stored dqkv (the qkv projection's bias gradient);
 // colsum_work: [B][3 H dh] floats of scratch (per-image sums, added in image order)
+// drop_p > 0: the backward of a forward pass with the same drop_p and drop_ld, whose seed is read from *seed_dev (device memory)
 extern "C" int nkb_attn_backward(int dtype, const void* qkv, const void* dout, const void* out, const float* lse, void* dqkv,
                                  int B, int T, int H, int dh, float scale, void* dqkv_q, float* q_state, float* colsum,
-                                 float* colsum_work, hipStream_t stream) {
+                                 float* colsum_work, float drop_p, const long long* seed_dev, int drop_ld, hipStream_t stream) {
     if (dqkv_q && !q_state) { nkb_set_error("attn_backward: the fp8 output needs its scaling state"); return 1; }
     if ((colsum == nullptr) != (colsum_work == nullptr)) { nkb_set_error("attn_backward: colsum and colsum_work go together"); return 1; }
     if (dtype != NKB_DT_BF16 || dh != DH || T > 16 * MAXKB || T < 1) {
         nkb_set_error("attn_backward: fused path needs bf16, head dim 64, T <= 256 (got dtype %d, dh %d, T %d)", dtype, dh, T);
         return 1;
     }
+    if (!attn_drop_args_ok("attn_backward", "seed_dev", drop_p, drop_ld, seed_dev, T)) return 1;
+    const bool dropping = drop_p > 0.f;
+    const AttnDrop drop = {dropout_thresh(drop_p), 1.f / (1.f - drop_p), 0ull, nullptr, seed_dev, drop_ld};
     const int nkb = (T + 15) / 16, rows = (nkb + 1) / 2 * 32;
     const int lds = 4 * rows * 128 + 2 * rows * 4 + (colsum ? 3 * (NKB_ATTN_BWD_THREADS / 64) * 64 * 4 : 0);
     NkbProfScope prof(NKB_K_ATTN, stream, 14.0 * B * H * (double)T * T * DH);     // S, dP twice; dQ, dK, dV once
-#define NKB_ATTN_BWDF(N)                                                                                                     \
-    case N: {                                                                                                                \
+#define NKB_ATTN_BWDF1(N, DR)                                                                                                \
+    {                                                                                                                        \
         static bool attr = false;                                                                                            \
-        if (!attr) { hipFuncSetAttribute((const void*)attn_bwd_fused_kernel<N>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); attr = true; } \
-        hipLaunchKernelGGL(attn_bwd_fused_kernel<N>, dim3(B * H), dim3(NKB_ATTN_BWD_THREADS), lds, stream, (const bf16_t*)qkv, (const bf16_t*)dout, (const bf16_t*)out, lse, \
-                           (bf16_t*)dqkv, T, H, scale, (unsigned char*)dqkv_q, q_state, colsum_work);                        \
-        break;                                                                                                               \
+        if (!attr) { hipFuncSetAttribute((const void*)attn_bwd_fused_kernel<N, DR>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); attr = true; } \
+        hipLaunchKernelGGL((attn_bwd_fused_kernel<N, DR>), dim3(B * H), dim3(NKB_ATTN_BWD_THREADS), lds, stream, (const bf16_t*)qkv, (const bf16_t*)dout, (const bf16_t*)out, lse, \
+                           (bf16_t*)dqkv, T, H, scale, (unsigned char*)dqkv_q, q_state, colsum_work, drop);                  \
     }
+#define NKB_ATTN_BWDF(N) case N: if (dropping) NKB_ATTN_BWDF1(N, true) else NKB_ATTN_BWDF1(N, false) break;
     switch (nkb) {
         NKB_ATTN_BWDF(1) NKB_ATTN_BWDF(2) NKB_ATTN_BWDF(3) NKB_ATTN_BWDF(4) NKB_ATTN_BWDF(5) NKB_ATTN_BWDF(6) NKB_ATTN_BWDF(7) NKB_ATTN_BWDF(8)
         NKB_ATTN_BWDF(9) NKB_ATTN_BWDF(10) NKB_ATTN_BWDF(11) NKB_ATTN_BWDF(12) NKB_ATTN_BWDF(13) NKB_ATTN_BWDF(14) NKB_ATTN_BWDF(15) NKB_ATTN_BWDF(16)
     }
 #undef NKB_ATTN_BWDF
+#undef NKB_ATTN_BWDF1
     int rc = nkb_check_launch("attn_backward");
     if (!rc && colsum) rc = nkb_launch_wgrad_reduce(colsum_work, 3ll * H * DH, B, colsum, 3ll * H * DH, /*assign=*/false, stream);
     return rc;

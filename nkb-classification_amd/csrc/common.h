@@ -56,6 +56,27 @@ __device__ __forceinline__ u32x4 pack8(const float* f) {
     return c;
 }
 
+// ---- dropout's counter-based generator: keep(seed, i) is a stateless hash of the 64-bit seed and the 64-bit element index i, so a
+// mask never has to be stored to be applied again.  ONE definition: nkb_dropout (csrc/transformer.hip) writes the mask bytes with it,
+// the fused attention kernels (csrc/attention.hip) regenerate the same decisions for the score elements a lane holds ----
+__host__ __device__ __forceinline__ unsigned mix32(unsigned h) {
+    h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
+    return h;
+}
+// an element is kept where its hash is >= this (p in [0, 1))
+__host__ __device__ __forceinline__ unsigned dropout_thresh(float p) {
+    return (unsigned)((double)p * 4294967296.0 > 4294967295.0 ? 4294967295.0 : (double)p * 4294967296.0);
+}
+// the hash in two steps: what depends on the high word of the index alone, then the rest (a caller that walks a short run of
+// indices computes the first step once per run)
+__host__ __device__ __forceinline__ unsigned dropout_hi_term(unsigned i_hi, unsigned seed_hi) { return i_hi * 0x9e3779b9u + seed_hi; }
+__host__ __device__ __forceinline__ unsigned dropout_hash(unsigned i_lo, unsigned hi_term, unsigned seed_lo) {
+    return mix32(mix32(i_lo ^ seed_lo) + hi_term);
+}
+__host__ __device__ __forceinline__ bool dropout_keep(unsigned long long i, unsigned seed_lo, unsigned seed_hi, unsigned thresh) {
+    return dropout_hash((unsigned)i, dropout_hi_term((unsigned)(i >> 32), seed_hi), seed_lo) >= thresh;
+}
+
 // ---- division by a runtime constant (32-bit, exact for n < 2^31) ----
 struct FastDiv {
     unsigned d, mul, sh;

@@ -1003,21 +1003,17 @@ extern "C" int nkb_colsum2d(int dtype, const void* x, float* out, long long rows
 // ---------------------------------------------------------------------------------------------------
 // Dropout with a counter-based generator (stateless hash of (seed, element index)): forward writes the keep mask,
 // backward re-applies it.  out = keep ? in / (1-p) : 0  (+ add).  Not bit-compatible with torch's Philox stream.
-__device__ __forceinline__ unsigned mix32(unsigned h) {
-    h ^= h >> 16; h *= 0x7feb352du; h ^= h >> 15; h *= 0x846ca68bu; h ^= h >> 16;
-    return h;
-}
+// (the generator itself — mix32, dropout_thresh, dropout_keep — is in common.h: the fused attention kernels regenerate this mask)
 template <typename T>
 __global__ void dropout_kernel(const T* __restrict__ in, const T* __restrict__ add, T* __restrict__ out,
                                unsigned char* __restrict__ mask, size_t n, float p, unsigned seed_lo, unsigned seed_hi,
                                int backward) {
     const float scale = 1.f / (1.f - p);
-    const unsigned thresh = (unsigned)((double)p * 4294967296.0 > 4294967295.0 ? 4294967295.0 : (double)p * 4294967296.0);
+    const unsigned thresh = dropout_thresh(p);
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         unsigned char keep;
         if (!backward) {
-            const unsigned r = mix32(mix32((unsigned)i ^ seed_lo) + (unsigned)(i >> 32) * 0x9e3779b9u + seed_hi);
-            keep = r >= thresh;
+            keep = dropout_keep(i, seed_lo, seed_hi, thresh);
             mask[i] = keep;
         } else {
             keep = mask[i];

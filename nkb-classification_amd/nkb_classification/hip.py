@@ -888,17 +888,20 @@ def dropout(dtype, backward, src, add, out, mask, n, p, seed=0):
     check(load().nkb_dropout(dtype, int(backward), ptr(src), ptr(add), ptr(out), ptr(mask), n, p, seed, stream()), "dropout")
 
 
-def attn_forward(dtype, qkv, out, lse, B, T, H, dh, scale, outq=None, q_state=None):
-    """outq / q_state: optional e4m3 copy of out for an fp8 projection (see fp8_quantize)."""
-    check(load().nkb_attn_forward(dtype, ptr(qkv), ptr(out), ptr(lse), B, T, H, dh, scale, ptr(outq), ptr(q_state), stream()),
-          "attn_forward")
+def attn_forward(dtype, qkv, out, lse, B, T, H, dh, scale, outq=None, q_state=None, drop_p=0.0, seed=0, drop_ld=0, seed_out=None):
+    """outq / q_state: optional e4m3 copy of out for an fp8 projection (see fp8_quantize).
+    drop_p > 0: attention dropout with nkb_dropout's mask of a [B*H, T, drop_ld] tensor under `seed` (a Seed from fresh_seed() is
+    redrawn at every plan replay); seed_out: one int64 on the device that receives the seed for attn_backward."""
+    check(load().nkb_attn_forward(dtype, ptr(qkv), ptr(out), ptr(lse), B, T, H, dh, scale, ptr(outq), ptr(q_state),
+                                  drop_p, seed, drop_ld, ptr(seed_out), stream()), "attn_forward")
 
 
-def attn_backward(dtype, qkv, dout, out, lse, dqkv, B, T, H, dh, scale, dqkv_q=None, q_state=None, colsum=None, colsum_work=None):
+def attn_backward(dtype, qkv, dout, out, lse, dqkv, B, T, H, dh, scale, dqkv_q=None, q_state=None, colsum=None, colsum_work=None,
+                  drop_p=0.0, seed_dev=None, drop_ld=0):
     """dqkv_q / q_state: optional e5m2 copy of dqkv for the fp8 qkv gradients.  colsum / colsum_work ([B][3 H dh] scratch):
-    colsum += the column sums of dqkv (the qkv bias gradient)."""
+    colsum += the column sums of dqkv (the qkv bias gradient).  drop_p / drop_ld: as in the forward call; seed_dev: its seed_out."""
     check(load().nkb_attn_backward(dtype, ptr(qkv), ptr(dout), ptr(out), ptr(lse), ptr(dqkv), B, T, H, dh, scale, ptr(dqkv_q),
-                                   ptr(q_state), ptr(colsum), ptr(colsum_work), stream()), "attn_backward")
+                                   ptr(q_state), ptr(colsum), ptr(colsum_work), drop_p, ptr(seed_dev), drop_ld, stream()), "attn_backward")
 
 
 def attn_backward_ds(dtype, qkv, dout, lse, P, dS, ldp, B, T, H, dh, scale, dq=None, ld_dq=0):

@@ -1376,20 +1376,30 @@ class HipEngine:
     def attention(self, key: str, qkv: torch.Tensor, B: int, T: int, H: int, train: bool, drop_p: float = 0.0,
                   q_for: Optional[str] = None) -> torch.Tensor:
         """softmax(q k^T / sqrt(dh)) v over all (image, head) pairs; qkv: [B*T, 3*D] laid out [which][head][dh].
-        drop_p: attention-probability dropout (timm Attention.attn_drop); active dropout takes the materialised path."""
+        drop_p: attention-probability dropout (timm Attention.attn_drop).  The fused kernels regenerate the keep mask from the seed
+        (the one nkb_dropout would write for the materialised P, row pitch Tp), so active dropout stays on them; only with the split
+        backward (_ATTN_FUSED_BWD off), which has no dropout flavour, it takes the materialised path."""
         D = qkv.shape[1] // 3
         dh = D // H
         Tp = _round_up(T, self.kte)
         attn_drop = train and drop_p > 0
-        if self.fused_attention and self.T == torch.bfloat16 and dh == 64 and T <= 256 and not attn_drop:
+        if self.fused_attention and self.T == torch.bfloat16 and dh == 64 and T <= 256 and (_ATTN_FUSED_BWD or not attn_drop):
             # fused kernel: scores and probabilities never reach HBM; only the per-row log-sum-exp is kept
             o = self.ws.get(key + ".o", (B * T, D), self.T)
             lse = self.ws.get(key + ".lse", (B * H, T), torch.float32)
             out = self._fp8_produce(q_for, (B * T, D), hip.E4M3) if (train and self.fp8) else None    # the projection's fp8 operand
-            hip.attn_forward(self.d, qkv, o, lse, B, T, H, dh, dh ** -0.5, outq=out[0] if out else None,
-                             q_state=out[1] if out else None)
+            drop = {}
+            if attn_drop:
+                # one host draw per site and step, where the materialised path's dropout(key + ".drop") draws its own; the backward
+                # pass, a plan of its own, takes the seed from the 8 bytes the forward kernel leaves on the device
+                drop = dict(p=drop_p, drop_ld=Tp, seed=self.ws.get(key + ".seed", (1,), torch.int64))
+                hip.attn_forward(self.d, qkv, o, lse, B, T, H, dh, dh ** -0.5, outq=out[0] if out else None,
+                                 q_state=out[1] if out else None, drop_p=drop_p, seed=hip.fresh_seed(), drop_ld=Tp, seed_out=drop["seed"])
+            else:
+                hip.attn_forward(self.d, qkv, o, lse, B, T, H, dh, dh ** -0.5, outq=out[0] if out else None,
+                                 q_state=out[1] if out else None)
             if train:
-                self.saved[key] = dict(qkv=qkv, lse=lse, o=o, B=B, T=T, H=H, fused=True)
+                self.saved[key] = dict(qkv=qkv, lse=lse, o=o, B=B, T=T, H=H, fused=True, **drop)
             return o
         S = self.ws.get("attn.S", (B * H, T, Tp), torch.float32)
         P = self.ws.get(key + ".P", (B * H, T, Tp), self.T)
@@ -1433,9 +1443,12 @@ class HipEngine:
                     work = self.ws.at_least("attn.colsum", B * 3 * D, torch.float32)
                     self._f8bias[q_for] = True
             hip.attn_backward(self.d, qkv, d_o, sv["o"], sv["lse"], dqkv, B, T, H, dh, dh ** -0.5,
-                              dqkv_q=out[0] if out else None, q_state=out[1] if out else None, colsum=csum, colsum_work=work)
+                              dqkv_q=out[0] if out else None, q_state=out[1] if out else None, colsum=csum, colsum_work=work,
+                              drop_p=sv.get("p", 0.0), seed_dev=sv.get("seed"), drop_ld=sv.get("drop_ld", 0))
             return dqkv
         if sv.get("fused"):
+            if sv.get("p"):
+                raise RuntimeError("attention_backward: the split backward kernels have no dropout flavour (forward ran with dropout fused)")
             # P and dS are recomputed in one pass (pad columns beyond roundup(T,16) stay zero from allocation)
             P = self.ws.get("attn.Pbwd", (B * H, T, Tp), self.T, zero=True)
             dS = self.ws.get("attn.dS", (B * H, T, Tp), self.T, zero=True)
