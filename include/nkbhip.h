@@ -30,6 +30,9 @@ typedef struct ihipStream_t* nkb_stream_t; /* hipStream_t */
 
 #define NKB_DT_F32 0
 #define NKB_DT_BF16 1
+/* `kind` of nkb_gelu / nkb_gelu_fwd_dgelu: the MLP activation of a transformer block */
+#define NKB_ACT_GELU 0       /* exact erf: x Phi(x) (timm nn.GELU()) */
+#define NKB_ACT_QUICK_GELU 1 /* x sigmoid(1.702 x) (timm QuickGELU: the OpenAI / MetaCLIP / DFN CLIP towers) */
 
 const char* nkb_last_error(void);
 int nkb_version(void);
@@ -325,7 +328,11 @@ int nkb_gemm_tn_batched(int dtype, const void* a, const void* b, void* out, int 
  * act 4: y = (xW^T) * aux (GELU backward with aux = gelu'(pre) kept by nkb_gelu_fwd_dgelu or by act 5).
  * act 5: y = gelu(xW^T+b), y2 = gelu'(xW^T+b): fc1 forward that leaves exactly what act 4 needs and never stores the pre-activation
  * (bf16 shapes of the 256 x 256 eight-phase core only: nkb_linear_gelu_fused_ok() == 1; erf by Abramowitz-Stegun 7.1.26,
- * |error| <= 1.5e-7, below the bf16 rounding of both outputs). */
+ * |error| <= 1.5e-7, below the bf16 rounding of both outputs).
+ * QuickGELU twins, q(v) = v / (1 + exp(-1.702 v)) and q'(v) = s (1 + 1.702 v (1 - s)) with s = q(v) / v: act 7 = act 1 (y2 = xW^T+b,
+ * y = q(y2)); act 8 = act 2 (y = (xW^T) * q'(aux)); act 9 = act 5 (y = q(xW^T+b), y2 = q'(xW^T+b); eight-phase shapes only, needs y2;
+ * bf16 by exp2 / rcp, results zero where the exponential overflows, never NaN for finite operands).  act 4 multiplies by whichever
+ * derivative was stored and serves both activations.  act 6 is unassigned and refused, as is every act >= 10. */
 int nkb_linear_gelu(int dtype, int act, const void* x, const void* w, const float* bias, const void* aux, void* y, void* y2,
                     int M, int K, int N, nkb_stream_t stream);
 int nkb_linear_gelu_fused_ok(int dtype, int M, int K, int N);
@@ -359,10 +366,11 @@ size_t nkb_layernorm_workspace_floats(int D); /* backward: optional scratch for 
  * nkb_layernorm takes). */
 int nkb_layernorm_param_reduce(float* workspace, int rows, int D, int planes, float* dgamma, float* dbeta, float* colsum,
                                nkb_stream_t stream);
-/* exact-erf GELU: dy == NULL -> out = gelu(x); else out = dy * gelu'(x) */
-/* forward that also stores gelu'(x) (timm Mlp.act, backward then is the act-4 epilogue of nkb_linear_gelu) */
-int nkb_gelu_fwd_dgelu(int dtype, const void* x, void* y, void* gp, long long n, nkb_stream_t stream);
-int nkb_gelu(int dtype, const void* x, const void* dy, void* out, long long n, nkb_stream_t stream);
+/* MLP activation, kind = NKB_ACT_GELU (exact erf) or NKB_ACT_QUICK_GELU (any other kind is refused, the message names `kind`):
+ * dy == NULL -> out = act(x); else out = dy * act'(x) */
+/* forward that also stores act'(x) (timm Mlp.act, backward then is the act-4 epilogue of nkb_linear_gelu); gp may be x (in place) */
+int nkb_gelu_fwd_dgelu(int dtype, const void* x, void* y, void* gp, long long n, int kind, nkb_stream_t stream);
+int nkb_gelu(int dtype, const void* x, const void* dy, void* out, long long n, int kind, nkb_stream_t stream);
 /* softmax over fp32 score rows (forward: p = softmax(scale*s); backward: ds = scale*p*(dp - sum dp*p)), zero padded to ldp */
 int nkb_attn_softmax(int dtype, int backward, const float* s, int lds, const void* p_in, void* out, int ldp,
                      long long rows, int cols, float scale, nkb_stream_t stream);

@@ -56,6 +56,46 @@ __device__ __forceinline__ u32x4 pack8(const float* f) {
     return c;
 }
 
+// ---- QuickGELU (the MLP activation of the OpenAI / MetaCLIP / DFN CLIP towers): u = x s with s = 1 / (1 + exp(-1.702 x)), and
+// u' = s (1 + 1.702 x (1 - s)).  ONE definition in two forms: the GEMM epilogues (csrc/gemm8p.hip, csrc/conv_igemm.hip) and the
+// elementwise kernels (csrc/transformer.hip) all take the pair from here.  For large negative x the exponential overflows to +inf:
+// then s = 1 / inf = 0 and both results are (signed) zeros.  The derivative is evaluated as s + 1.702 (u (1 - s)): |u| <= |x| and
+// |u (1 - s)| < 0.3 are finite for every finite x, where 1.702 x itself overflows from |x| = 2e38 on and would meet a zero factor
+// (inf * 0).  The only infinity that can appear is the exponential, and it is consumed by the reciprocal: no finite x gives a NaN.
+constexpr float NKB_QGELU_A = 1.702f;
+// packed form for bf16 outputs, two elements per instruction: two quarter-rate instructions per element (exp2, rcp) and six packed
+// multiplies / adds / FMAs per PAIR (g8_gelu2's erf chain needs thirteen, and two sign transfers)
+__device__ __forceinline__ void quick_gelu2(nkb_f2 x, nkb_f2& u, nkb_f2& du) {
+    constexpr float c = (float)(-1.702 * 1.4426950408889634);                                 // -1.702 log2(e)
+    const nkb_f2 one = {1.f, 1.f};
+    const nkb_f2 z = x * (nkb_f2){c, c};
+    const nkb_f2 den = (nkb_f2){__builtin_amdgcn_exp2f(z[0]), __builtin_amdgcn_exp2f(z[1])} + one;   // 1 + exp(-1.702 x), +inf at most
+    const nkb_f2 s = {__builtin_amdgcn_rcpf(den[0]), __builtin_amdgcn_rcpf(den[1])};
+    u = x * s;
+    du = __builtin_elementwise_fma((nkb_f2){NKB_QGELU_A, NKB_QGELU_A}, u * (one - s), s);
+}
+// fp32 form (the parity mode): libm's expf and a true division
+__device__ __forceinline__ void quick_gelu_f32(float x, float& u, float& du) {
+    const float s = 1.f / (1.f + expf(-NKB_QGELU_A * x));
+    u = x * s;
+    du = s + NKB_QGELU_A * (u * (1.f - s));
+}
+// N (even) values in the dtype's form: T = bf16_t packed, T = float exact; u / du may be x
+template <typename T, int N>
+__device__ __forceinline__ void quick_gelu_n(const float* x, float* u, float* du) {
+    if constexpr (sizeof(T) == 2) {
+#pragma unroll
+        for (int e = 0; e < N; e += 2) {
+            nkb_f2 uu, dd;
+            quick_gelu2((nkb_f2){x[e], x[e + 1]}, uu, dd);
+            u[e] = uu[0]; u[e + 1] = uu[1]; du[e] = dd[0]; du[e + 1] = dd[1];
+        }
+    } else {
+#pragma unroll
+        for (int e = 0; e < N; ++e) { const float xe = x[e]; quick_gelu_f32(xe, u[e], du[e]); }
+    }
+}
+
 // ---- dropout's counter-based generator: keep(seed, i) is a stateless hash of the 64-bit seed and the 64-bit element index i, so a
 // mask never has to be stored to be applied again.  ONE definition: nkb_dropout (csrc/transformer.hip) writes the mask bytes with it,
 // the fused attention kernels (csrc/attention.hip) regenerate the same decisions for the score elements a lane holds ----

@@ -742,6 +742,24 @@ __global__ __launch_bounds__(256, ((BNB && TC == 128) || TC == 64) ? 3 : 1) void
                 v[e] *= 0.5f * (1.f + erff(a * 0.70710678118654752f)) + a * 0.3989422804014327f * expf(-0.5f * a * a);
             }
         }
+        else if (!BNB && p.act == 7) {     // QuickGELU forward (common.h), the twin of act 1: pre-activation to y2, quickgelu(pre) to y
+            T* o2 = (T*)p.y2 + orow * p.ldy + co;
+            float dq[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                v[e] = DT<T>::rnd(v[e]);
+                if (co + e < p.Cout) DT<T>::st(o2 + e, v[e]);
+            }
+            quick_gelu_n<T, 8>(v, v, dq);
+        } else if (!BNB && p.act == 8) {   // QuickGELU backward, the twin of act 2: multiply by quickgelu'(pre-activation read from aux)
+            const T* ax = (const T*)p.aux + orow * p.ldy + co;
+            float a[8], uq[8], dq[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) a[e] = (co + e < p.Cout) ? DT<T>::ld(ax + e) : 0.f;
+            quick_gelu_n<T, 8>(a, uq, dq);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] *= dq[e];
+        }
         else if (!BNB && p.act == 3) {     // ReLU6 backward (unicom Mlp.act): aux = the clamped forward output u; 0 < u < 6 <=> 0 < pre < 6
             const T* ax = (const T*)p.aux + orow * p.ldy + co;
 #pragma unroll
@@ -1548,6 +1566,8 @@ extern "C" int nkb_conv_dgrad_s2class(int dtype, const void* dy, const void* w_c
 //   act 4: y = (x W^T) * aux                                  (fc2 data-gradient, aux = gelu'(pre) from nkb_gelu_fwd_dgelu)
 //   act 5: pre = x W^T + b -> y = gelu(pre), y2 = gelu'(pre)  (fc1 forward when the backward pass is act 4: the pre-activation is
 //          never stored and the separate nkb_gelu_fwd_dgelu pass disappears; eight-phase core only — nkb_linear_gelu_fused_ok)
+//   act 7 / 8 / 9: acts 1 / 2 / 5 with QuickGELU (x sigmoid(1.702 x), common.h) in place of the erf form: the MLP of the OpenAI-weight
+//          CLIP towers.  act 4 multiplies by whichever derivative was stored; act 6 is unassigned.
 extern "C" int nkb_linear_gelu_fused_ok(int dtype, int M, int K, int N) {
     if (dtype != NKB_DT_BF16 || (long long)M * K * 2 >= 0xFFFFFF00ll || (long long)N * K * 2 >= 0xFFFFFF00ll || (long long)M * N >= (1ll << 31)) return 0;
     ConvParams p = gemm_geometry(M, K, N, K, K, N);
@@ -1573,21 +1593,22 @@ extern "C" int nkb_linear_gelu(int dtype, int act, const void* x, const void* w,
                                void* y2, int M, int K, int N, hipStream_t stream) {
     const int esz = dtype == NKB_DT_BF16 ? 2 : 4;
     const int kte = 128 / esz;
-    if ((dtype != NKB_DT_BF16 && dtype != NKB_DT_F32) || (act < 1 || act > 5) || K % kte != 0 || N % 8 != 0) {
+    if ((dtype != NKB_DT_BF16 && dtype != NKB_DT_F32) || (act < 1 || act > 9 || act == 6) || K % kte != 0 || N % 8 != 0) {
         nkb_set_error("linear_gelu: unsupported dtype/act/shape (K=%d N=%d)", K, N);
         return 1;
     }
-    if (act == 5 && (!y2 || !nkb_linear_gelu_fused_ok(dtype, M, K, N))) {
-        nkb_set_error("linear_gelu: act 5 needs y2 and a shape of the eight-phase core (nkb_linear_gelu_fused_ok)");
+    if ((act == 5 || act == 9) && (!y2 || !nkb_linear_gelu_fused_ok(dtype, M, K, N))) {
+        nkb_set_error("linear_gelu: act %d needs y2 and a shape of the eight-phase core (nkb_linear_gelu_fused_ok)", act);
         return 1;
     }
+    if (act == 7 && !y2) { nkb_set_error("linear_gelu: act 7 needs y2 for the pre-activation"); return 1; }
     if ((long long)M * K * esz >= 0xFFFFFF00ll || (long long)N * K * esz >= 0xFFFFFF00ll || (long long)M * N >= (1ll << 31)) {
         nkb_set_error("linear_gelu: operand exceeds the 4 GiB buffer-addressing range");
         return 1;
     }
     ConvParams p = gemm_geometry(M, K, N, K, K, N);
     p.x = x; p.w = w; p.y = y; p.bias = bias; p.act = act; p.aux = aux; p.y2 = y2;
-    NkbProfScope prof(act == 1 || act == 5 ? NKB_K_CONV_FWD : NKB_K_CONV_DGRAD, stream, 2.0 * M * (double)N * K);
+    NkbProfScope prof(act == 1 || act == 5 || act == 7 || act == 9 ? NKB_K_CONV_FWD : NKB_K_CONV_DGRAD, stream, 2.0 * M * (double)N * K);
     if (nkb_gemm8p_eligible(p, dtype, 1)) return nkb_launch_gemm8p(p, stream);
     return launch_conv<EPI_GENERAL>(p, dtype, narrow_tile(N), stream);
 }

@@ -23,9 +23,10 @@ struct ConvParams {
     FastDiv divPQ = {}, divQ = {};
     // batched GEMM (attention): blockIdx.y = zo*inner + zi; element offsets zo*s?o + zi*s?i on x / w / y
     int add_h = 0, add_w = 0;   // > 0: `add` is [N][add_h][add_w][ldadd] on the stride-2 sub-grid of the output (zero elsewhere)
-    int act = 0;        // 0 none, 1 GELU forward (pre-activation also stored to y2), 2 multiply by gelu'(aux)
-    const void* aux = nullptr;    // [M][ldy] pre-activation for act 2
-    void* y2 = nullptr;           // [M][ldy] pre-activation output for act 1
+    int act = 0;        // 0 none, 1 GELU forward (pre-activation also stored to y2), 2 multiply by gelu'(aux); 3 - 5 and the QuickGELU
+                        // twins 7 / 8 / 9 of 1 / 2 / 5: see nkb_linear_gelu (conv_igemm.hip)
+    const void* aux = nullptr;    // [M][ldy] pre-activation for act 2 / 8 (acts 3, 4: the operand of that epilogue)
+    void* y2 = nullptr;           // [M][ldy] pre-activation output for act 1 / 7 (acts 5, 9: the activation's derivative)
     int stride_w = 1, pad_w = 0; // mode 0: horizontal stride / padding (== stride / pad except for the packed stem)
     int stem_cprw = 0;  // > 0: packed-stem addressing, 16-byte chunks per filter row inside one 128-byte k-tile (see
                         //      nkb_stem_conv); x is [N][H][W/rpt][one chunk], W is passed pre-multiplied by rpt = 8/stem_cprw

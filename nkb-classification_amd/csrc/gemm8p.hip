@@ -53,8 +53,9 @@ struct G8Params {
     float* stats;         // optional [ceil(M/128)][2][N] sums of y and y^2 per 128 pixel rows (BatchNorm partials, same
                           // granularity as the 128 x 128 kernel so nkb_conv_gemm_stat_tiles stays a function of (M, Cout))
     int M, N, K, ldx, ldw, ldy, ldadd;
-    int relu;             // 0 none, 1 ReLU, 2 ReLU6, 3 GELU (exact form, see g8_gelu) with gelu'(pre) as a second bf16 output
-    bf16_t* y2;           // relu == 3: gelu'(product + bias), [M][ldy] — what the fc2 data gradient multiplies by (aux_mode 0)
+    int relu;             // 0 none, 1 ReLU, 2 ReLU6, 3 GELU (exact form, see g8_gelu2) with gelu'(pre) as a second bf16 output — in the
+                          // kernels of the QuickGELU flavour (ACT == 1) 3 is QuickGELU with quickgelu'(pre) as that second output
+    bf16_t* y2;           // relu == 3: act'(product + bias), [M][ldy] — what the fc2 data gradient multiplies by (aux_mode 0)
     int tilesM, tilesN, group_m;
     // fp8 operands (F8 != 0): x and w hold one byte per element (K = bytes per row); the fp32 result is multiplied by
     // *deq_x * *deq_w (the per-tensor dequantisation factors, device floats) before bias / residual
@@ -190,9 +191,19 @@ __device__ __forceinline__ float g8_sload(const float* ptr) {
 // F8: 0 = bf16 operands (k-tile = 64 elements); 1 = fp8 e4m3 x e4m3, 2 = W e4m3 x X e5m2 (data gradients): a k-tile is the
 // same 128 bytes per row = 128 elements and the two 16-byte fragments of a row go into ONE v_mfma_f32_16x16x128_f8f6f4 (twice
 // the bf16 rate; g8_mma128) — half the LDS / L2 bytes and half the MFMA cycles per FLOP of the bf16 form.
-template <bool DIRECT, int F8 = 0, bool QOUT = false>
+// OPS: bits 1:0 = F8 above; bit 2 = ACT, what `relu == 3` computes — 0 exact-erf GELU (g8_gelu2), 1 QuickGELU (quick_gelu2,
+// common.h): OPS = G8_QGELU is the bf16 kernel of the QuickGELU flavour.  A COMPILE-TIME flavour with an instance of its own: these
+// kernels sit at the edge of their register file, and a run-time branch between two activations inside the existing instances
+// would be one more value live across their epilogues.  It rides in the operand parameter so that the existing instances keep their
+// template arguments, their names and — F8 and ACT being constants either way — their code, instruction for instruction
+// (moving the body into an inlined function with a fourth parameter changed their register allocation).
+constexpr int G8_QGELU = 4;
+template <bool DIRECT, int OPS = 0, bool QOUT = false>
 __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const G8Params p) {
+    constexpr int F8 = OPS & 3, ACT = OPS >> 2;
+    static_assert(F8 <= 2 && ACT <= 1, "operand formats 0-2, activation flavours 0-1");
     static_assert(!QOUT || (DIRECT && F8 != 0), "the quantised second output belongs to the persistent fp8 kernels");
+    static_assert(ACT == 0 || (F8 == 0 && !QOUT), "the QuickGELU flavour is a bf16 kernel");
     constexpr int ESZ = F8 ? 1 : 2;               // bytes per operand element
     constexpr int KE = 128 / ESZ;                 // elements per k-tile row
     constexpr int CE = 16 / ESZ;                  // elements per 16-byte chunk
@@ -540,7 +551,8 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const G8Params p) {
 #pragma unroll
                 for (int e = 0; e < 8; e += 2) {
                     g8_f32x2 uu, dd;
-                    g8_gelu2((g8_f32x2){v[e], v[e + 1]}, uu, dd);
+                    if constexpr (ACT == 1) quick_gelu2((g8_f32x2){v[e], v[e + 1]}, uu, dd);
+                    else g8_gelu2((g8_f32x2){v[e], v[e + 1]}, uu, dd);
                     v[e] = uu[0]; v[e + 1] = uu[1]; dv[e] = dd[0]; dv[e + 1] = dd[1];
                 }
                 dpk = pack8(dv);
@@ -846,6 +858,10 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const G8Params p) {
                 if (p.align_epi && wr == 0) NKB_BARRIER();
                 G8_STAMP(5);
                 const bool fullt = tile_m * 256 + 256 <= p.M;
+                if constexpr (ACT != 0) {         // the flavour serves one launch: fc1 forward, no residual, no saved operand
+                    if (fullt) epilogue(G8I<1>{}, G8I<0>{}, G8I<0>{}, G8I<3>{});
+                    else epilogue(G8I<0>{}, G8I<-1>{}, G8I<-1>{}, G8I<-1>{});
+                } else
                 if constexpr (QOUT) {             // the two producers of the fp8 train step; everything else takes the run-time form
                     if (fullt && !p.add && !p.aux && p.relu == 2) epilogue(G8I<1>{}, G8I<0>{}, G8I<0>{}, G8I<2>{});
                     else if (fullt && !p.add && p.aux && p.aux_mode == 1 && p.relu == 0) epilogue(G8I<1>{}, G8I<0>{}, G8I<2>{}, G8I<0>{});
@@ -944,7 +960,8 @@ __global__ __launch_bounds__(512, 1) void gemm8p_kernel(const G8Params p) {
 #pragma unroll
                         for (int e = 0; e < 8; e += 2) {
                             g8_f32x2 uu, dd;
-                            g8_gelu2((g8_f32x2){v[e], v[e + 1]}, uu, dd);
+                            if constexpr (ACT == 1) quick_gelu2((g8_f32x2){v[e], v[e + 1]}, uu, dd);
+                            else g8_gelu2((g8_f32x2){v[e], v[e + 1]}, uu, dd);
                             v[e] = uu[0]; v[e + 1] = uu[1]; dv[e] = dd[0]; dv[e + 1] = dd[1];
                         }
                         *(u32x4*)(p.y2 + (size_t)m * p.ldy + co) = pack8(dv);
@@ -1007,8 +1024,9 @@ struct G8RParams {
     float* slab; unsigned* ticket;
 };
 
-template <int RF>                                 // 16-row fragments per wave: the kernel covers 64 RF rows
+template <int RFA>                                // bits 1:0 = RF, 16-row fragments per wave: the kernel covers 64 RF rows; bit 2 = ACT as in gemm8p_kernel
 __global__ __launch_bounds__(512) void gemm8p_ragged_kernel(const G8RParams p) {
+    constexpr int RF = RFA & 3, ACT = RFA >> 2;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 15, g = lane >> 4;
     const int cb = blockIdx.x, sp = blockIdx.y;
     const int ks = p.K / p.S, k0 = sp * ks;       // (K % (32 S) == 0: checked by the host)
@@ -1139,7 +1157,8 @@ __global__ __launch_bounds__(512) void gemm8p_ragged_kernel(const G8RParams p) {
 #pragma unroll
             for (int e = 0; e < 16; e += 2) {
                 g8_f32x2 uu, dd;
-                g8_gelu2((g8_f32x2){v[e], v[e + 1]}, uu, dd);
+                if constexpr (ACT == 1) quick_gelu2((g8_f32x2){v[e], v[e + 1]}, uu, dd);
+                else g8_gelu2((g8_f32x2){v[e], v[e + 1]}, uu, dd);
                 v[e] = uu[0]; v[e + 1] = uu[1]; dv[e] = dd[0]; dv[e + 1] = dd[1];
             }
 #pragma unroll
@@ -1173,9 +1192,9 @@ bool nkb_gemm8p_eligible(const ConvParams& p, int dtype, int batch) {
     if (!(p.R == 1 && p.S == 1 && p.stride == 1 && p.stride_w == 1 && p.pad == 0 && p.pad_w == 0 && p.stem_cprw == 0 &&
           p.sub_h == 0 && p.H == p.P && p.W == p.Q && p.mode == 0))
         return false;
-    if (p.out_f32 || p.add_h != 0 || p.add_bits != nullptr || (p.y2 != nullptr && p.act != 5) || (p.act != 0 && p.act != 3 && p.act != 4 && p.act != 5))
+    if (p.out_f32 || p.add_h != 0 || p.add_bits != nullptr || (p.y2 != nullptr && p.act != 5 && p.act != 9) || (p.act != 0 && p.act != 3 && p.act != 4 && p.act != 5 && p.act != 9))
         return false;
-    if (p.act == 5 && (p.y2 == nullptr || p.stats || p.add || p.relu)) return false;
+    if ((p.act == 5 || p.act == 9) && (p.y2 == nullptr || p.stats || p.add || p.relu)) return false;
     if (p.Cout % 256 != 0 || p.Cin % 64 != 0 || p.Cin < 128 || p.ldy % 8 != 0 || p.ldx % 8 != 0 || p.ldw % 8 != 0) return false;
     if (p.add && p.ldadd % 8 != 0) return false;
     if (p.add && p.stats) return false;
@@ -1216,6 +1235,7 @@ static void g8_lds_once() {
         constexpr int lds = 2 * 4 * 128 * 128 + 4096 + 64 + 4096;
         hipFuncSetAttribute((const void*)gemm8p_kernel<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         hipFuncSetAttribute((const void*)gemm8p_kernel<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+        hipFuncSetAttribute((const void*)gemm8p_kernel<true, G8_QGELU>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         hipFuncSetAttribute((const void*)gemm8p_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         hipFuncSetAttribute((const void*)gemm8p_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         hipFuncSetAttribute((const void*)gemm8p_kernel<true, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
@@ -1262,7 +1282,7 @@ static bool g8r_scratch(hipStream_t stream, size_t floats, float** slabs, unsign
 }
 
 // Launches the companion for rows [M0, M0 + R) of the problem in `p` (pointers of the FULL problem); false: shape not served.
-static bool g8_launch_ragged(const G8Params& p, int M0, int R, hipStream_t stream) {
+static bool g8_launch_ragged(const G8Params& p, int M0, int R, bool qgelu, hipStream_t stream) {
     if (R < 1 || R > 128 || p.N % G8R_COLS != 0 || p.row_scale || p.yq || p.mask_in || p.mask_out || p.colpart || p.stats) return false;
     const int blocks = p.N / G8R_COLS;
     if (blocks > 128) return false;
@@ -1283,7 +1303,10 @@ static bool g8_launch_ragged(const G8Params& p, int M0, int R, hipStream_t strea
     q.slab = slabs; q.ticket = tickets;
     const dim3 grid((unsigned)blocks, (unsigned)S);
     nkb_count_launch(NKB_LAUNCH_GEMM8P_RAGGED);
-    if (R <= 64) hipLaunchKernelGGL(gemm8p_ragged_kernel<1>, grid, dim3(512), 0, stream, q);
+    if (qgelu) {
+        if (R <= 64) hipLaunchKernelGGL(gemm8p_ragged_kernel<1 | G8_QGELU>, grid, dim3(512), 0, stream, q);
+        else hipLaunchKernelGGL(gemm8p_ragged_kernel<2 | G8_QGELU>, grid, dim3(512), 0, stream, q);
+    } else if (R <= 64) hipLaunchKernelGGL(gemm8p_ragged_kernel<1>, grid, dim3(512), 0, stream, q);
     else hipLaunchKernelGGL(gemm8p_ragged_kernel<2>, grid, dim3(512), 0, stream, q);
     return true;
 }
@@ -1299,9 +1322,10 @@ int nkb_launch_gemm8p(const ConvParams& cp, hipStream_t stream, const float* row
     p.row_scale = row_scale; p.div_rows = make_fastdiv(row_scale && rows_per_sample > 0 ? (unsigned)rows_per_sample : 1u);
     p.mask_out = nullptr; p.mask_in = nullptr; p.colpart = nullptr;
     p.M = cp.M; p.N = cp.Cout; p.K = cp.Cin; p.ldx = cp.ldx; p.ldw = cp.ldw; p.ldy = cp.ldy; p.ldadd = cp.ldadd;
-    p.relu = cp.act == 5 ? 3 : cp.relu;
-    p.y2 = cp.act == 5 ? (bf16_t*)cp.y2 : nullptr;
-    if (cp.act == 5) {
+    const bool fused_act = cp.act == 5 || cp.act == 9, qgelu = cp.act == 9;   // act 9: act 5 on the kernels of the QuickGELU flavour
+    p.relu = fused_act ? 3 : cp.relu;
+    p.y2 = fused_act ? (bf16_t*)cp.y2 : nullptr;
+    if (fused_act) {
         constexpr int ga = 1;
         p.align_epi = ga;
     }
@@ -1325,13 +1349,14 @@ int nkb_launch_gemm8p(const ConvParams& cp, hipStream_t stream, const float* row
         const int R = p.M % 256;
         if (g8_ragged_on && R != 0 && p.tilesM >= 2 && g8_rounds((p.tilesM - 1) * p.tilesN, cus) < g8_rounds(tiles, cus)) {
             G8Params full = p;
-            if (g8_launch_ragged(full, p.M - R, R, stream)) {
+            if (g8_launch_ragged(full, p.M - R, R, qgelu, stream)) {
                 p.M -= R; p.tilesM -= 1;
                 p.group_m = (gm_env > 1 && wbytes > 3.0e6 && p.tilesN >= 6 && p.tilesM >= 2 * gm_env) ? gm_env : 0;
             }
         }
         const int tiles1 = p.tilesM * p.tilesN;
-        hipLaunchKernelGGL(gemm8p_kernel<true>, dim3((unsigned)g8_grid(tiles1, cus)), dim3(512), lds, stream, p);
+        if (qgelu) hipLaunchKernelGGL((gemm8p_kernel<true, G8_QGELU>), dim3((unsigned)g8_grid(tiles1, cus)), dim3(512), lds, stream, p);
+        else hipLaunchKernelGGL(gemm8p_kernel<true>, dim3((unsigned)g8_grid(tiles1, cus)), dim3(512), lds, stream, p);
     } else
         hipLaunchKernelGGL(gemm8p_kernel<false>, dim3((unsigned)tiles), dim3(512), lds, stream, p);
     return nkb_check_launch("gemm8p");

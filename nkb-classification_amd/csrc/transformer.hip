@@ -703,7 +703,8 @@ extern "C" int nkb_layernorm(int dtype, int backward, const void* in, long long 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// GELU (exact erf form, timm's nn.GELU()): forward y = gelu(x); backward dx = dy * gelu'(x)
+// GELU (exact erf form, timm's nn.GELU()) and QuickGELU (timm's QuickGELU, the OpenAI CLIP towers): forward y = act(x); backward
+// dx = dy * act'(x)
 template <typename T> struct V16;      // 16-byte vectors: 8 bf16 / 4 fp32
 template <> struct V16<bf16_t> {
     static constexpr int N = 8;
@@ -716,61 +717,86 @@ template <> struct V16<float> {
     __device__ static __forceinline__ void st(float* p, const float* f) { *(f32x4*)p = (f32x4){f[0], f[1], f[2], f[3]}; }
 };
 
-template <typename T>
+template <typename T, int KIND>      // KIND 0: exact erf; 1: QuickGELU (common.h)
 __global__ void gelu_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ out, size_t nvec) {
     constexpr int N = V16<T>::N;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (size_t)gridDim.x * blockDim.x) {
         float a[N], g[N], o[N];
         V16<T>::ld(x + i * N, a);
         if (dy) V16<T>::ld(dy + i * N, g);
+        if constexpr (KIND == 1) {
+            float d[N];
+            quick_gelu_n<T, N>(a, o, d);
+#pragma unroll
+            for (int e = 0; e < N; ++e) o[e] = dy ? g[e] * d[e] : o[e];
+        } else {
 #pragma unroll
         for (int e = 0; e < N; ++e) {
             const float c = 0.5f * (1.f + erff(a[e] * 0.70710678118654752f));
             o[e] = dy ? g[e] * (c + a[e] * 0.3989422804014327f * expf(-0.5f * a[e] * a[e])) : a[e] * c;
         }
+        }
         V16<T>::st(out + i * N, o);
     }
 }
-extern "C" int nkb_gelu(int dtype, const void* x, const void* dy, void* out, long long n, hipStream_t stream) {
+// kind (both entry points): NKB_ACT_GELU (0) exact erf, NKB_ACT_QUICK_GELU (1) x * sigmoid(1.702 x)
+static bool gelu_kind_ok(const char* who, int kind) {
+    if (kind == NKB_ACT_GELU || kind == NKB_ACT_QUICK_GELU) return true;
+    nkb_set_error("%s: unknown activation kind %d (0 = exact-erf GELU, 1 = QuickGELU)", who, kind);
+    return false;
+}
+extern "C" int nkb_gelu(int dtype, const void* x, const void* dy, void* out, long long n, int kind, hipStream_t stream) {
     const int N = dtype == NKB_DT_BF16 ? 8 : 4;
+    if (!gelu_kind_ok("gelu", kind)) return 1;
     if (n % N) { nkb_set_error("gelu: element count %lld not a multiple of %d", n, N); return 1; }
     NkbProfScope prof(NKB_K_GELU, stream, 0);
     size_t nvec = (size_t)n / N, g = (nvec + 255) / 256;
     if (g > 256 * 16) g = 256 * 16;
     if (g < 1) g = 1;
-    if (dtype == NKB_DT_BF16) hipLaunchKernelGGL(gelu_kernel<bf16_t>, dim3((unsigned)g), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)out, nvec);
-    else hipLaunchKernelGGL(gelu_kernel<float>, dim3((unsigned)g), dim3(256), 0, stream, (const float*)x, (const float*)dy, (float*)out, nvec);
+    if (kind == NKB_ACT_QUICK_GELU) {
+        if (dtype == NKB_DT_BF16) hipLaunchKernelGGL((gelu_kernel<bf16_t, 1>), dim3((unsigned)g), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)out, nvec);
+        else hipLaunchKernelGGL((gelu_kernel<float, 1>), dim3((unsigned)g), dim3(256), 0, stream, (const float*)x, (const float*)dy, (float*)out, nvec);
+    } else if (dtype == NKB_DT_BF16) hipLaunchKernelGGL((gelu_kernel<bf16_t, 0>), dim3((unsigned)g), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)out, nvec);
+    else hipLaunchKernelGGL((gelu_kernel<float, 0>), dim3((unsigned)g), dim3(256), 0, stream, (const float*)x, (const float*)dy, (float*)out, nvec);
     return nkb_check_launch("gelu");
 }
 
 // GELU forward that also emits gelu'(x) (same dtype): the backward pass then is a plain multiply, done in the epilogue of
 // the fc2 data-gradient GEMM (nkb_linear_gelu act 4) instead of a separate erf/exp pass over dy and x.
-template <typename T>
+template <typename T, int KIND>
 __global__ void gelu_fwd_dgelu_kernel(const T* x, T* __restrict__ y, T* gp, size_t nvec) {   // gp may alias x (in place)
     constexpr int N = V16<T>::N;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (size_t)gridDim.x * blockDim.x) {
         float a[N], o[N], d[N];
         V16<T>::ld(x + i * N, a);
+        if constexpr (KIND == 1) {
+            quick_gelu_n<T, N>(a, o, d);
+        } else {
 #pragma unroll
         for (int e = 0; e < N; ++e) {
             const float c = 0.5f * (1.f + erff(a[e] * 0.70710678118654752f));
             o[e] = a[e] * c;
             d[e] = c + a[e] * 0.3989422804014327f * expf(-0.5f * a[e] * a[e]);
         }
+        }
         V16<T>::st(y + i * N, o);
         V16<T>::st(gp + i * N, d);
     }
 }
-extern "C" int nkb_gelu_fwd_dgelu(int dtype, const void* x, void* y, void* gp, long long n, hipStream_t stream) {
+extern "C" int nkb_gelu_fwd_dgelu(int dtype, const void* x, void* y, void* gp, long long n, int kind, hipStream_t stream) {
     const int N = dtype == NKB_DT_BF16 ? 8 : 4;
     if (dtype != NKB_DT_BF16 && dtype != NKB_DT_F32) { nkb_set_error("gelu_fwd_dgelu: bad dtype %d", dtype); return 1; }
+    if (!gelu_kind_ok("gelu_fwd_dgelu", kind)) return 1;
     if (n % N) { nkb_set_error("gelu_fwd_dgelu: element count %lld not a multiple of %d", n, N); return 1; }
     NkbProfScope prof(NKB_K_GELU, stream, 0);
     size_t nvec = (size_t)n / N, g = (nvec + 255) / 256;
     if (g > 256 * 16) g = 256 * 16;
     if (g < 1) g = 1;
-    if (dtype == NKB_DT_BF16) hipLaunchKernelGGL(gelu_fwd_dgelu_kernel<bf16_t>, dim3((unsigned)g), dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)y, (bf16_t*)gp, nvec);
-    else hipLaunchKernelGGL(gelu_fwd_dgelu_kernel<float>, dim3((unsigned)g), dim3(256), 0, stream, (const float*)x, (float*)y, (float*)gp, nvec);
+    if (kind == NKB_ACT_QUICK_GELU) {
+        if (dtype == NKB_DT_BF16) hipLaunchKernelGGL((gelu_fwd_dgelu_kernel<bf16_t, 1>), dim3((unsigned)g), dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)y, (bf16_t*)gp, nvec);
+        else hipLaunchKernelGGL((gelu_fwd_dgelu_kernel<float, 1>), dim3((unsigned)g), dim3(256), 0, stream, (const float*)x, (float*)y, (float*)gp, nvec);
+    } else if (dtype == NKB_DT_BF16) hipLaunchKernelGGL((gelu_fwd_dgelu_kernel<bf16_t, 0>), dim3((unsigned)g), dim3(256), 0, stream, (const bf16_t*)x, (bf16_t*)y, (bf16_t*)gp, nvec);
+    else hipLaunchKernelGGL((gelu_fwd_dgelu_kernel<float, 0>), dim3((unsigned)g), dim3(256), 0, stream, (const float*)x, (float*)y, (float*)gp, nvec);
     return nkb_check_launch("gelu_fwd_dgelu");
 }
 

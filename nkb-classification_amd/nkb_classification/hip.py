@@ -834,8 +834,13 @@ def layernorm_ws(D):
     return load().nkb_layernorm_workspace_floats(D)
 
 
-def gelu(dtype, x, dy, out, n):
-    check(load().nkb_gelu(dtype, ptr(x), ptr(dy), ptr(out), n, stream()), "gelu")
+# `kind` of gelu / gelu_fwd_dgelu (NKB_ACT_* of include/nkbhip.h): the MLP activation of a transformer block
+ACT_GELU, ACT_QUICK_GELU = 0, 1
+ACT_KINDS = {"gelu": ACT_GELU, "quick_gelu": ACT_QUICK_GELU}
+
+
+def gelu(dtype, x, dy, out, n, kind=ACT_GELU):
+    check(load().nkb_gelu(dtype, ptr(x), ptr(dy), ptr(out), n, kind, stream()), "gelu")
 
 
 def splitk_reduce(dtype, partial, splits, M, N, y, ldy, bias, stats):
@@ -852,8 +857,8 @@ def image_prep(src, sizes, flags, out, B, Hs, Ws, Ho, Wo, mean, std, fill=0.0):
                                 C.cast(sd, C.c_void_p), float(fill), stream()), "image_prep")
 
 
-def gelu_fwd_dgelu(dtype, x, y, gp, n):
-    check(load().nkb_gelu_fwd_dgelu(dtype, ptr(x), ptr(y), ptr(gp), n, stream()), "gelu_fwd_dgelu")
+def gelu_fwd_dgelu(dtype, x, y, gp, n, kind=ACT_GELU):
+    check(load().nkb_gelu_fwd_dgelu(dtype, ptr(x), ptr(y), ptr(gp), n, kind, stream()), "gelu_fwd_dgelu")
 
 
 def relu6(dtype, x, dy, out, n):

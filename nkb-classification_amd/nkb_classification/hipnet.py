@@ -1174,9 +1174,19 @@ class HipEngine:
             hip.linear_gelu(self.d, act, g, self._wd[id(lin.weight)], None, aux, d_pre, None, M, N, K)
         return d_pre
 
-    def linear_gelu_keep_derivative(self, key: str, key_act: str, x: torch.Tensor, lin: nn.Linear, train: bool):
-        """u = gelu(x @ W^T + b) AND gelu'(pre) from the fc1 GEMM's epilogue (the pre-activation is never stored; the separate
-        elementwise pass over it is gone); saved like linear() + gelu(keep_derivative=True), so the backward pass is
+    @staticmethod
+    def mlp_act_kind(mlp) -> int:
+        """The activation of a timm Mlp as hip.ACT_*: `mlp.act` = "gelu" | "quick_gelu"; a module without the attribute (ConvNeXt,
+        every ViT built before QuickGELU existed here) is exact-erf GELU.  Anything else is an error, never a silent GELU."""
+        name = getattr(mlp, "act", "gelu")
+        if name not in hip.ACT_KINDS:
+            raise ValueError(f"unknown MLP activation {name!r}: one of {sorted(hip.ACT_KINDS)}")
+        return hip.ACT_KINDS[name]
+
+    def linear_gelu_keep_derivative(self, key: str, key_act: str, x: torch.Tensor, lin: nn.Linear, train: bool,
+                                    kind: int = hip.ACT_GELU):
+        """u = act(x @ W^T + b) AND act'(pre) (kind: hip.ACT_GELU / hip.ACT_QUICK_GELU) from the fc1 GEMM's epilogue (the
+        pre-activation is never stored; the separate elementwise pass over it is gone); saved like linear() + gelu(keep_derivative=True), so the backward pass is
         linear_backward_through_act + linear_backward.  Returns None when the shape is not one of the eight-phase
         core's (the caller then takes the two-kernel path)."""
         M, K = x.shape
@@ -1186,19 +1196,23 @@ class HipEngine:
             return None
         u = self.ws.get(key_act + ".y", (M, N), self.T)
         gp = self.ws.get(key + ".y", (M, N), self.T)            # (the buffer the plain path keeps the pre-activation / derivative in)
-        hip.linear_gelu(self.d, 5, x, self.w_fwd(lin.weight), self.arena.param_flat(lin.bias), None, u, gp, M, K, N)
+        act = 9 if kind == hip.ACT_QUICK_GELU else 5
+        hip.linear_gelu(self.d, act, x, self.w_fwd(lin.weight), self.arena.param_flat(lin.bias), None, u, gp, M, K, N)
         self.saved[key] = dict(x=x, lin=lin)
         self.saved[key_act] = dict(gp=gp)
         return u
 
     def mlp_gelu_fc1(self, prefix: str, h: torch.Tensor, mlp, train: bool) -> torch.Tensor:
-        """First half of a timm Mlp (ViT and ConvNeXt blocks): fc1 -> exact-erf GELU -> drop1, under the keys <prefix>.fc1, .act and
-        .mlp_drop.  gelu'(pre) is kept in place of the pre-activation (from the fc1 epilogue where the shape allows it, else from
-        the GELU pass) unless drop1 is active: the dropout mask sits between fc2's data gradient and the GELU's then."""
+        """First half of a timm Mlp (ViT and ConvNeXt blocks): fc1 -> activation (mlp_act_kind(mlp): exact-erf GELU unless the module
+        says QuickGELU) -> drop1, under the keys <prefix>.fc1, .act and .mlp_drop.  act'(pre) is kept in place of the pre-activation
+        (from the fc1 epilogue where the shape allows it, else from the activation pass) unless drop1 is active: the dropout mask sits
+        between fc2's data gradient and the activation's then."""
         keep = not (train and mlp.drop1.p > 0)
-        u = self.linear_gelu_keep_derivative(prefix + ".fc1", prefix + ".act", h, mlp.fc1, train) if keep else None
+        kind = self.mlp_act_kind(mlp)
+        kw = {"kind": kind} if kind != hip.ACT_GELU else {}       # (a GELU module makes the calls it always made, argument for argument)
+        u = self.linear_gelu_keep_derivative(prefix + ".fc1", prefix + ".act", h, mlp.fc1, train, **kw) if keep else None
         if u is None:
-            u = self.gelu(prefix + ".act", self.linear(prefix + ".fc1", h, mlp.fc1, train), train, keep_derivative=keep)
+            u = self.gelu(prefix + ".act", self.linear(prefix + ".fc1", h, mlp.fc1, train), train, keep_derivative=keep, **kw)
         return self.dropout(prefix + ".mlp_drop", u, mlp.drop1.p, train)
 
     def mlp_gelu_fc1_backward(self, prefix: str, g2: torch.Tensor) -> torch.Tensor:
@@ -1284,23 +1298,27 @@ class HipEngine:
         launch()
         return out
 
-    def gelu(self, key: str, x: torch.Tensor, train: bool, keep_derivative: bool = False) -> torch.Tensor:
-        """keep_derivative: the forward pass also stores gelu'(x), overwriting x (the pre-activation is not needed again);
+    def gelu(self, key: str, x: torch.Tensor, train: bool, keep_derivative: bool = False,
+             kind: int = hip.ACT_GELU) -> torch.Tensor:
+        """The MLP activation (kind: hip.ACT_GELU exact erf, hip.ACT_QUICK_GELU).
+        keep_derivative: the forward pass also stores act'(x), overwriting x (the pre-activation is not needed again);
         the backward pass is then linear_backward_through_act instead of gelu_backward."""
         y = self.ws.get(key + ".y", x.shape, self.T)
+        kw = {"kind": kind} if kind != hip.ACT_GELU else {}
         if train and keep_derivative:
-            hip.gelu_fwd_dgelu(self.d, x, y, x, x.numel())
+            hip.gelu_fwd_dgelu(self.d, x, y, x, x.numel(), **kw)
             self.saved[key] = dict(gp=x)
             return y
-        hip.gelu(self.d, x, None, y, x.numel())
+        hip.gelu(self.d, x, None, y, x.numel(), **kw)
         if train:
-            self.saved[key] = dict(x=x)
+            self.saved[key] = dict(x=x, kind=kind)         # (gelu_backward differentiates the activation the forward pass applied)
         return y
 
     def gelu_backward(self, key: str, g: torch.Tensor, slot: str) -> torch.Tensor:
-        x = self.saved[key]["x"]
+        sv = self.saved[key]
+        x, kind = sv["x"], sv.get("kind", hip.ACT_GELU)
         dx = self.scratch(slot, x.shape)
-        hip.gelu(self.d, x, g, dx, x.numel())
+        hip.gelu(self.d, x, g, dx, x.numel(), **({"kind": kind} if kind != hip.ACT_GELU else {}))
         return dx
 
     def _ones(self, n: int) -> torch.Tensor:

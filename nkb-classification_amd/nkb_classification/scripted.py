@@ -101,13 +101,23 @@ class _Attention(nn.Module):
 
 
 class _Mlp(nn.Module):
-    def __init__(self, dim: int, hidden: int):
+    """act: "gelu" (exact erf) or "quick_gelu" (x * sigmoid(1.702 x): the OpenAI-weight CLIP towers)."""
+
+    def __init__(self, dim: int, hidden: int, act: str = "gelu"):
         super().__init__()
+        if act not in ("gelu", "quick_gelu"):
+            raise ValueError(f"unknown MLP activation {act!r}")
+        self.quick_gelu = act == "quick_gelu"
         self.fc1 = nn.Linear(dim, hidden)
         self.fc2 = nn.Linear(hidden, dim)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        return self.fc2(torch.nn.functional.gelu(self.fc1(x)))
+        h = self.fc1(x)
+        if self.quick_gelu:
+            h = h * torch.sigmoid(1.702 * h)
+        else:
+            h = torch.nn.functional.gelu(h)
+        return self.fc2(h)
 
 
 class _LayerScale(nn.Module):
@@ -120,13 +130,14 @@ class _LayerScale(nn.Module):
 
 
 class _Block(nn.Module):
-    def __init__(self, dim: int, heads: int, mlp_ratio: float, ln_eps: float = 1e-6, init_values: Optional[float] = None):
+    def __init__(self, dim: int, heads: int, mlp_ratio: float, ln_eps: float = 1e-6, init_values: Optional[float] = None,
+                 act: str = "gelu"):
         super().__init__()
         self.norm1 = nn.LayerNorm(dim, eps=ln_eps)
         self.attn = _Attention(dim, heads)
         self.ls1 = _LayerScale(dim, init_values) if init_values is not None else nn.Identity()
         self.norm2 = nn.LayerNorm(dim, eps=ln_eps)
-        self.mlp = _Mlp(dim, int(dim * mlp_ratio))
+        self.mlp = _Mlp(dim, int(dim * mlp_ratio), act)
         self.ls2 = _LayerScale(dim, init_values) if init_values is not None else nn.Identity()
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -144,10 +155,11 @@ class _PatchEmbed(nn.Module):
 
 
 class _ViT(nn.Module):
-    """timm VisionTransformer with its pre_norm / init_values (LayerScale) / no_embed_class options (nkb_classification/vit.py)."""
+    """timm VisionTransformer with its pre_norm / init_values (LayerScale) / no_embed_class / act_layer options
+    (nkb_classification/vit.py)."""
 
     def __init__(self, img: int, patch: int, dim: int, depth: int, heads: int, mlp_ratio: float = 4.0, pre_norm: bool = False,
-                 ln_eps: float = 1e-6, init_values: Optional[float] = None, no_embed_class: bool = False):
+                 ln_eps: float = 1e-6, init_values: Optional[float] = None, no_embed_class: bool = False, act: str = "gelu"):
         super().__init__()
         self.num_features = dim
         self.no_embed_class = no_embed_class
@@ -155,7 +167,7 @@ class _ViT(nn.Module):
         self.cls_token = nn.Parameter(torch.zeros(1, 1, dim))
         self.pos_embed = nn.Parameter(torch.zeros(1, (img // patch) ** 2 + (0 if no_embed_class else 1), dim))
         self.norm_pre = nn.LayerNorm(dim, eps=ln_eps) if pre_norm else nn.Identity()
-        self.blocks = nn.Sequential(*[_Block(dim, heads, mlp_ratio, ln_eps, init_values) for _ in range(depth)])
+        self.blocks = nn.Sequential(*[_Block(dim, heads, mlp_ratio, ln_eps, init_values, act) for _ in range(depth)])
         self.norm = nn.LayerNorm(dim, eps=ln_eps)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -313,7 +325,7 @@ def _backbone_like(hip_backbone) -> nn.Module:
     if getattr(hip_backbone, "family", "") == "vit":
         return _ViT(hip_backbone.img, hip_backbone.patch, hip_backbone.num_features, len(hip_backbone.blocks), hip_backbone.heads,
                     pre_norm=hip_backbone.pre_norm, ln_eps=hip_backbone.ln_eps, init_values=hip_backbone.init_values,
-                    no_embed_class=hip_backbone.no_embed_class)
+                    no_embed_class=hip_backbone.no_embed_class, act=getattr(hip_backbone, "act", "gelu"))
     if getattr(hip_backbone, "family", "") == "convnext":
         return _ConvNeXt(list(hip_backbone.depths), list(hip_backbone.dims))
     layers = [len(getattr(hip_backbone, f"layer{i}")) for i in (1, 2, 3, 4)]

@@ -5,11 +5,15 @@ Reference call site: timm.create_model("vit_base_patch16_224", ...) at
 /root/reference/nkb_classification/model.py:82; architecture per SURVEY.md §8 A8 (LayerNorm eps 1e-6, qkv with
 bias, exact-erf GELU, pre-norm residual blocks, x[:, 0] of the final norm as the embedding).
 
-Three constructor options of timm's VisionTransformer cover the foundation-model members (restated from memory of timm, parity
+Four constructor options of timm's VisionTransformer cover the foundation-model members (restated from memory of timm, parity
 unpinned; the twin they are checked against is tests/vit_options_reference.py):
   pre_norm         CLIP image towers: bias-free patch projection, LayerNorm `norm_pre` in front of block 0 (ln_eps 1e-5)
   init_values      DINOv2 / DeiT-III: LayerScale, x + ls1(attn(norm1(x))), x + ls2(mlp(norm2(x))), gamma initialised to the value
   no_embed_class   DeiT-III: pos_embed covers the patch tokens only; the class token is prepended without one
+  act              "gelu" (exact erf) | "quick_gelu" (x * sigmoid(1.702 x)): the CLIP towers trained by OpenAI, MetaCLIP and DFN.
+                   timm keeps them under names of their own (`*_clip_quickgelu_*`, act_layer="quick_gelu") because the activation is
+                   part of the model: a QuickGELU checkpoint in the GELU twin silently evaluates another function.  No parameter
+                   depends on it, so the keys and shapes are the GELU twin's (twin: tests/vit_quickgelu_reference.py)
 """
 from __future__ import annotations
 
@@ -38,8 +42,9 @@ class _Attention(_ParamOnly):
 
 
 class _Mlp(_ParamOnly):
-    def __init__(self, dim, hidden):
+    def __init__(self, dim, hidden, act="gelu"):
         super().__init__()
+        self.act = act                                            # what HipEngine.mlp_gelu_fc1 applies between fc1 and fc2
         self.fc1 = nn.Linear(dim, hidden)
         self.drop1 = nn.Dropout(0.0)
         self.fc2 = nn.Linear(hidden, dim)
@@ -53,14 +58,14 @@ class _LayerScale(_ParamOnly):
 
 
 class _Block(_ParamOnly):
-    def __init__(self, dim, heads, mlp_ratio, ln_eps=1e-6, init_values=None):
+    def __init__(self, dim, heads, mlp_ratio, ln_eps=1e-6, init_values=None, act="gelu"):
         super().__init__()
         self.norm1 = nn.LayerNorm(dim, eps=ln_eps)
         self.attn = _Attention(dim, heads)
         if init_values is not None:
             self.ls1 = _LayerScale(dim, init_values)
         self.norm2 = nn.LayerNorm(dim, eps=ln_eps)
-        self.mlp = _Mlp(dim, int(dim * mlp_ratio))
+        self.mlp = _Mlp(dim, int(dim * mlp_ratio), act)
         if init_values is not None:
             self.ls2 = _LayerScale(dim, init_values)
 
@@ -69,8 +74,11 @@ class HipViT(_ParamOnly):
     family = "vit"
 
     def __init__(self, img=224, patch=16, dim=768, depth=12, heads=12, mlp_ratio=4.0, pre_norm=False, ln_eps=1e-6,
-                 init_values=None, no_embed_class=False):
+                 init_values=None, no_embed_class=False, act="gelu"):
         super().__init__()
+        if act not in hip.ACT_KINDS:
+            raise ValueError(f"unknown MLP activation {act!r}: one of {sorted(hip.ACT_KINDS)}")
+        self.act = act
         self.num_features = dim
         self.img, self.patch, self.heads = img, patch, heads
         self.pre_norm, self.ln_eps, self.init_values, self.no_embed_class = pre_norm, ln_eps, init_values, no_embed_class
@@ -82,7 +90,7 @@ class HipViT(_ParamOnly):
         self.pos_drop = nn.Dropout(0.0)
         if pre_norm:
             self.norm_pre = nn.LayerNorm(dim, eps=ln_eps)
-        self.blocks = nn.Sequential(*[_Block(dim, heads, mlp_ratio, ln_eps, init_values) for _ in range(depth)])
+        self.blocks = nn.Sequential(*[_Block(dim, heads, mlp_ratio, ln_eps, init_values, act) for _ in range(depth)])
         self.norm = nn.LayerNorm(dim, eps=ln_eps)
         self.head_drop = nn.Dropout(0.0)
         nn.init.normal_(self.cls_token, std=1e-6)
@@ -229,6 +237,11 @@ _VITS = {
     "vit_base_patch16_clip_224": dict(img=224, patch=16, dim=768, depth=12, heads=12, **_CLIP),
     "vit_large_patch14_clip_224": dict(img=224, patch=14, dim=1024, depth=24, heads=16, **_CLIP),
     "vit_large_patch14_clip_336": dict(img=336, patch=14, dim=1024, depth=24, heads=16, **_CLIP),
+    # the same towers with QuickGELU in the MLP (the OpenAI ViT-B/32, B/16, L/14, L/14@336 weights; MetaCLIP, DFN): same keys and shapes
+    "vit_base_patch32_clip_quickgelu_224": dict(img=224, patch=32, dim=768, depth=12, heads=12, **_CLIP, act="quick_gelu"),
+    "vit_base_patch16_clip_quickgelu_224": dict(img=224, patch=16, dim=768, depth=12, heads=12, **_CLIP, act="quick_gelu"),
+    "vit_large_patch14_clip_quickgelu_224": dict(img=224, patch=14, dim=1024, depth=24, heads=16, **_CLIP, act="quick_gelu"),
+    "vit_large_patch14_clip_quickgelu_336": dict(img=336, patch=14, dim=1024, depth=24, heads=16, **_CLIP, act="quick_gelu"),
     "vit_small_patch14_dinov2": dict(img=518, patch=14, dim=384, depth=12, heads=6, init_values=1e-5),
     "vit_base_patch14_dinov2": dict(img=518, patch=14, dim=768, depth=12, heads=12, init_values=1e-5),
     "vit_large_patch14_dinov2": dict(img=518, patch=14, dim=1024, depth=24, heads=16, init_values=1e-5),
@@ -240,6 +253,9 @@ _VITS = {
     "vit_tiny192_test": dict(img=64, patch=16, dim=192, depth=2, heads=3),       # reduced ViT-Tiny width (T = 17)
     "vit_tiny192_p32_test": dict(img=96, patch=32, dim=192, depth=1, heads=3),   # ... with 32-pixel patches (T = 10)
     "vit_clip_test": dict(img=64, patch=16, dim=128, depth=2, heads=2, **_CLIP),                  # reduced CLIP tower (T = 17)
+    "vit_clip_quickgelu_test": dict(img=64, patch=16, dim=128, depth=2, heads=2, **_CLIP, act="quick_gelu"),     # ... with QuickGELU
+    # the same inside the eight-phase (fc1 epilogue, act 9) and fp8 envelopes (dim 256)
+    "vit_clip_quickgelu_f8_test": dict(img=64, patch=16, dim=256, depth=2, heads=4, **_CLIP, act="quick_gelu"),
     "vit_dinov2_test": dict(img=70, patch=14, dim=128, depth=2, heads=2, init_values=1e-5),       # reduced DINOv2 (T = 26)
     "deit3_test": dict(img=64, patch=16, dim=128, depth=2, heads=2, **_DEIT3),                    # reduced DeiT-III (T = 17)
     "vit_dinov2_long_test": dict(img=238, patch=14, dim=128, depth=1, heads=2, init_values=1e-5),  # T = 290: unfused attention

@@ -1,13 +1,16 @@
 """The eight GEMM launches of one ViT-B/16 block (forward + data gradients, batch 256) with the epilogues the train step gives them,
 run as a chain over block-sized buffers (> 256 MB per pass: nothing stays in the Infinity Cache between passes), per-launch device
-times from the library's HIP-event profiler.  `python scripts/gemm8p_epi_bench.py [reps]`; environment switches are inherited, so
-alternating builds / settings in one process pool is `scripts/ab_lib.sh`'s job."""
+times from the library's HIP-event profiler.  `python scripts/gemm8p_epi_bench.py [reps] [fc1 act]`; fc1 act 5 (default) is the exact-erf
+GELU epilogue, 9 its QuickGELU twin (the chain is otherwise the same: act 4 multiplies by whichever derivative fc1 stored).  Environment
+switches are inherited, so alternating builds / settings in one process pool is `scripts/ab_lib.sh`'s job."""
 import os, sys, statistics, torch
 R = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, os.path.join(R, "nkb-classification_amd"))
 from nkb_classification import hip
 dev = "cuda"; T = torch.bfloat16; d = hip.BF16
 M, D, H3, H4 = 256 * 197, 768, 2304, 3072
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 12
+fc1_act = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+assert fc1_act in (5, 9), fc1_act
 g = torch.Generator(device=dev).manual_seed(1)
 rn = lambda *s: torch.randn(*s, device=dev, generator=g).to(T)
 x, res, o = rn(M, D), rn(M, D), rn(M, D)
@@ -20,7 +23,8 @@ gemm = lambda xx, ww, yy, K, N, **kw: hip.conv_gemm(d, 0, xx, ww, yy, N=M, H=1, 
 OPS = [
     ("qkv fwd  768->2304 +bias      ", 2.0 * M * D * H3, lambda: gemm(x, w_qkv, qkv, D, H3, bias=b3)),
     ("proj fwd 768->768  +bias +res ", 2.0 * M * D * D, lambda: gemm(o, w_proj, y1, D, D, bias=b1, add=res, ldadd=D)),
-    ("fc1 fwd  768->3072 gelu, gelu'", 2.0 * M * D * H4, lambda: hip.linear_gelu(d, 5, y1, w_fc1, b4, None, u, du, M, D, H4)),
+    ("fc1 fwd  768->3072 gelu, gelu'" if fc1_act == 5 else "fc1 fwd  768->3072 quickgelu, '", 2.0 * M * D * H4,
+     lambda: hip.linear_gelu(d, fc1_act, y1, w_fc1, b4, None, u, du, M, D, H4)),
     ("fc2 fwd  3072->768 +bias +res ", 2.0 * M * D * H4, lambda: gemm(u, w_fc2, y2, H4, D, bias=b1, add=y1, ldadd=D)),
     ("fc2 dgrad 768->3072 * gelu'   ", 2.0 * M * D * H4, lambda: hip.linear_gelu(d, 4, y2, wd_fc2, None, du, dpre, None, M, D, H4)),
     ("fc1 dgrad 3072->768           ", 2.0 * M * D * H4, lambda: gemm(dpre, wd_fc1, dh, H4, D)),
