@@ -238,10 +238,35 @@ int nkb_conv_dgrad_bn_cat(int dtype, const void* g, int ldg, int K1, const void*
                           const float* mean, float* stats, long long M, int Cout, int ldy, nkb_stream_t stream);
 size_t nkb_bn_backward_workspace_floats(long long rows, int C);
 
-/* MaxPool2d(3, 2, 1) and global average pool, forward (backward=0) / backward (backward=1), NHWC. */
+/* MaxPool2d(3, 2, 1), forward (backward=0) / backward (backward=1), NHWC. */
 int nkb_maxpool3x3s2(int dtype, int backward, const void* in, void* out, unsigned char* idx, int N, int H, int W, int C,
                      nkb_stream_t stream);
-int nkb_avgpool(int dtype, int backward, const void* in, void* out, int N, int HW, int C, nkb_stream_t stream);
+/* The per-image reductions over [N][HW][C] rows (NHWC), one launch per call; `mode` picks the pass.
+ * Global average pool: NKB_POOL_AVG_FWD in [N][HW][C] -> out [N][C]; NKB_POOL_AVG_BWD in [N][C] -> out [N][HW][C] (g / HW broadcast).
+ * These two read no operand behind C.
+ * Global response normalisation (timm GlobalResponseNorm, the ConvNeXt V2 MLP; csrc/grn.hip), C = the hidden width, a multiple of
+ * 64 up to 4096, N * HW * C < 2^31, eps > 0, weight / bias / dweight / dbias fp32 [C], sumsq fp32 [N][C], all sums fp32 in an order
+ * that depends on the shape alone:
+ *   NKB_GRN_FWD_REDUCE  sumsq[b][c] = sum_p in^2                                                   (in = u)
+ *   NKB_GRN_FWD_APPLY   out = u * (1 + weight[c] * G / m[b]) + bias[c],  G = sqrt(sumsq), m[b] = mean_c G + eps   (in = u)
+ *   NKB_GRN_BWD_REDUCE  workspace <- P[b][c] = sum_p g u and Q[b][c] = sum_p g                      (in = g, in2 = u)
+ *   NKB_GRN_BWD_APPLY   out = (g s + u t) (* mul, a tensor like u, may be NULL), s as above, t = dG / G (0 where sumsq == 0),
+ *                       dG = weight P / m - (sum_c weight P G) / (C m^2); reads P of the workspace, leaves m[b] in it   (in = g, in2 = u)
+ *   NKB_GRN_PARAM       dweight[c] += sum_b (G / m[b]) P, dbias[c] += sum_b Q (either may be NULL); reads the workspace the two
+ *                       backward passes left
+ * The backward modes need workspace_floats >= 2 * N * C + N. */
+enum NkbPoolMode {
+    NKB_POOL_AVG_FWD = 0,
+    NKB_POOL_AVG_BWD = 1,
+    NKB_GRN_FWD_REDUCE = 2,
+    NKB_GRN_FWD_APPLY = 3,
+    NKB_GRN_BWD_REDUCE = 4,
+    NKB_GRN_BWD_APPLY = 5,
+    NKB_GRN_PARAM = 6
+};
+int nkb_avgpool(int dtype, int mode, const void* in, void* out, int N, int HW, int C, const void* in2, const float* weight,
+                const float* bias, float* sumsq, float* dweight, float* dbias, const void* mul, float eps, float* workspace,
+                long long workspace_floats, nkb_stream_t stream);
 /* ResNet stem tail in one pass (timm resnet.py forward_features: bn1 -> act1 -> maxpool, reached from
  * nkb_classification/model.py:84).  c is the raw conv1 output [N][H][W][C].
  * backward=0: y_or_g (out) = maxpool3x3s2(relu(c*scale+shift)) [N][P][Q][C], idx = winning window slot.

@@ -56,6 +56,28 @@ __device__ __forceinline__ u32x4 pack8(const float* f) {
     return c;
 }
 
+// ---- one 16-byte chunk of an activation tensor (8 bf16 / 4 fp32) as floats: the vector I/O of the HBM-bound kernels ----
+template <typename T> struct Chunk;
+template <> struct Chunk<bf16_t> {
+    static constexpr int N = 8;
+    typedef u32x4 Raw;                                      // a chunk as loaded: kept packed while the load is in flight
+    __device__ static __forceinline__ Raw ldraw(const bf16_t* p) { return *(const u32x4*)p; }
+    __device__ static __forceinline__ void unpack(const Raw& r, float* f) { unpack8(r, f); }
+    __device__ static __forceinline__ void load(const bf16_t* p, float* f) { unpack8(*(const u32x4*)p, f); }
+    __device__ static __forceinline__ void store(bf16_t* p, const float* f) { *(u32x4*)p = pack8(f); }
+};
+template <> struct Chunk<float> {
+    static constexpr int N = 4;
+    typedef f32x4 Raw;
+    __device__ static __forceinline__ Raw ldraw(const float* p) { return *(const f32x4*)p; }
+    __device__ static __forceinline__ void unpack(const Raw& r, float* f) { f[0] = r[0]; f[1] = r[1]; f[2] = r[2]; f[3] = r[3]; }
+    __device__ static __forceinline__ void load(const float* p, float* f) {
+        const f32x4 v = *(const f32x4*)p;
+        f[0] = v[0]; f[1] = v[1]; f[2] = v[2]; f[3] = v[3];
+    }
+    __device__ static __forceinline__ void store(float* p, const float* f) { *(f32x4*)p = (f32x4){f[0], f[1], f[2], f[3]}; }
+};
+
 // ---- QuickGELU (the MLP activation of the OpenAI / MetaCLIP / DFN CLIP towers): u = x s with s = 1 / (1 + exp(-1.702 x)), and
 // u' = s (1 + 1.702 x (1 - s)).  ONE definition in two forms: the GEMM epilogues (csrc/gemm8p.hip, csrc/conv_igemm.hip) and the
 // elementwise kernels (csrc/transformer.hip) all take the pair from here.  For large negative x the exponential overflows to +inf:
@@ -169,6 +191,11 @@ int nkb_launch_wgrad_reduce(const float* part, long long slab, int splits, float
 int nkb_launch_wgrad_reduce2(const float* part, long long slab, int splits, float* dst, long long n, const float* part2, long long slab2,
                              float* dst2, long long n2, bool assign, hipStream_t stream);
 
+// the global-response-normalisation passes of nkb_avgpool (csrc/grn.hip): modes NKB_GRN_* of include/nkbhip.h
+int nkb_grn(int dtype, int mode, const void* in, void* out, int N, int HW, int C, const void* in2, const float* weight, const float* bias,
+            float* sumsq, float* dweight, float* dbias, const void* mul, float eps, float* workspace, long long workspace_floats,
+            hipStream_t stream);
+
 // bumps a launch counter of nkb_kernel_launches (api.hip); which: an NkbLaunchCounter of include/nkbhip.h
 void nkb_count_launch(int which);
 
@@ -206,7 +233,10 @@ struct NkbProfScope {
     X(NKB_K_LAYER_SCALE, "layer_scale") \
     X(NKB_K_STEM3_FWD, "stem3_fwd") \
     X(NKB_K_STEM3_DGRAD, "stem3_dgrad") \
-    X(NKB_K_AVGPOOL2, "avgpool2x2")
+    X(NKB_K_AVGPOOL2, "avgpool2x2") \
+    X(NKB_K_GRN_REDUCE, "grn_reduce") \
+    X(NKB_K_GRN_APPLY, "grn_apply") \
+    X(NKB_K_GRN_PARAM, "grn_param")
 #define NKB_KERNEL_ID_ENUM(id, name) id,
 enum NkbKernelId { NKB_KERNEL_IDS(NKB_KERNEL_ID_ENUM) NKB_K_COUNT };
 #undef NKB_KERNEL_ID_ENUM

@@ -11,27 +11,6 @@ static inline unsigned grid_for(size_t work_items, int block = 256, unsigned cap
     return (unsigned)g;
 }
 
-template <typename T> struct Chunk;
-template <> struct Chunk<bf16_t> {
-    static constexpr int N = 8;
-    typedef u32x4 Raw;                                      // a chunk as loaded: kept packed while the load is in flight
-    __device__ static __forceinline__ Raw ldraw(const bf16_t* p) { return *(const u32x4*)p; }
-    __device__ static __forceinline__ void unpack(const Raw& r, float* f) { unpack8(r, f); }
-    __device__ static __forceinline__ void load(const bf16_t* p, float* f) { unpack8(*(const u32x4*)p, f); }
-    __device__ static __forceinline__ void store(bf16_t* p, const float* f) { *(u32x4*)p = pack8(f); }
-};
-template <> struct Chunk<float> {
-    static constexpr int N = 4;
-    typedef f32x4 Raw;
-    __device__ static __forceinline__ Raw ldraw(const float* p) { return *(const f32x4*)p; }
-    __device__ static __forceinline__ void unpack(const Raw& r, float* f) { f[0] = r[0]; f[1] = r[1]; f[2] = r[2]; f[3] = r[3]; }
-    __device__ static __forceinline__ void load(const float* p, float* f) {
-        const f32x4 v = *(const f32x4*)p;
-        f[0] = v[0]; f[1] = v[1]; f[2] = v[2]; f[3] = v[3];
-    }
-    __device__ static __forceinline__ void store(float* p, const float* f) { *(f32x4*)p = (f32x4){f[0], f[1], f[2], f[3]}; }
-};
-
 // NC consecutive per-channel fp32 constants as 16-byte loads (a thread owns NC consecutive channels; one scalar load per
 // channel costs a whole wave-wide gather each and used to dominate the small BatchNorm launches)
 static inline int env_int(const char* name, int dflt) {
@@ -691,7 +670,13 @@ __global__ void avgpool_bwd_kernel(const T* __restrict__ g, T* __restrict__ dx, 
         Chunk<T>::store(dx + i * NC, v);
     }
 }
-extern "C" int nkb_avgpool(int dtype, int backward, const void* in, void* out, int N, int HW, int C, hipStream_t stream) {
+extern "C" int nkb_avgpool(int dtype, int mode, const void* in, void* out, int N, int HW, int C, const void* in2, const float* weight,
+                           const float* bias, float* sumsq, float* dweight, float* dbias, const void* mul, float eps, float* workspace,
+                           long long workspace_floats, hipStream_t stream) {
+    if (mode < NKB_POOL_AVG_FWD || mode > NKB_GRN_PARAM) { nkb_set_error("avgpool: bad mode %d", mode); return 1; }
+    if (mode >= NKB_GRN_FWD_REDUCE)
+        return nkb_grn(dtype, mode, in, out, N, HW, C, in2, weight, bias, sumsq, dweight, dbias, mul, eps, workspace, workspace_floats, stream);
+    const int backward = mode;
     const int n = dtype == NKB_DT_BF16 ? 8 : 4;
     if (C % n) { nkb_set_error("avgpool: C=%d not a multiple of %d", C, n); return 1; }
     NkbProfScope prof(NKB_K_AVGPOOL, stream, 0);

@@ -568,8 +568,48 @@ def maxpool(dtype, backward, src, dst, idx, N, H, W, C_):
     check(load().nkb_maxpool3x3s2(dtype, int(backward), ptr(src), ptr(dst), ptr(idx), N, H, W, C_, stream()), "maxpool")
 
 
+# enum NkbPoolMode of the header: the passes of nkb_avgpool ({"NKB_POOL_AVG_FWD": 0, ..., "NKB_GRN_PARAM": 6})
+_POOL_MODES = cabi.parse_enum(_HEADER, "NkbPoolMode")
+
+
+def _pool(what, dtype, mode, src, dst, N, HW, C_, in2=None, weight=None, bias=None, sumsq=None, dweight=None, dbias=None, mul=None,
+          eps=0.0, workspace=None):
+    check(load().nkb_avgpool(dtype, _POOL_MODES[mode], ptr(src), ptr(dst), N, HW, C_, ptr(in2), ptr(weight), ptr(bias), ptr(sumsq),
+                             ptr(dweight), ptr(dbias), ptr(mul), eps, ptr(workspace), workspace.numel() if workspace is not None else 0,
+                             stream()), what)
+
+
 def avgpool(dtype, backward, src, dst, N, HW, C_):
-    check(load().nkb_avgpool(dtype, int(backward), ptr(src), ptr(dst), N, HW, C_, stream()), "avgpool")
+    _pool("avgpool", dtype, "NKB_POOL_AVG_BWD" if backward else "NKB_POOL_AVG_FWD", src, dst, N, HW, C_)
+
+
+def grn_workspace(N, HW, C_) -> int:
+    """Floats of fp32 workspace grn_backward / grn_param need: the tables P, Q [N][C] and m [N] (include/nkbhip.h, nkb_avgpool)."""
+    return 2 * N * C_ + N
+
+
+def grn(dtype, u, weight, bias, out, sumsq, N, HW, C_, eps=1e-6, workspace=None):
+    """Global response normalisation over [N][HW][C] rows, two launches: sumsq [N][C] fp32 (kept for backward), then
+    out = u * (1 + weight * G / mean_c G) + bias.  The forward pass needs no workspace."""
+    _pool("grn", dtype, "NKB_GRN_FWD_REDUCE", u, None, N, HW, C_, sumsq=sumsq, eps=eps)
+    _pool("grn", dtype, "NKB_GRN_FWD_APPLY", u, out, N, HW, C_, weight=weight, bias=bias, sumsq=sumsq, eps=eps)
+
+
+def grn_backward(dtype, g, u, weight, sumsq, out, dweight, dbias, N, HW, C_, eps=1e-6, mul=None, workspace=None):
+    """out = d(loss)/du (* mul, e.g. the activation derivative in front of the GRN); dweight / dbias are accumulated into unless
+    both are None (grn_param makes that launch on its own, on another stream, from the same workspace).  workspace: at least
+    grn_workspace(N, HW, C) fp32."""
+    _pool("grn_backward", dtype, "NKB_GRN_BWD_REDUCE", g, None, N, HW, C_, in2=u, sumsq=sumsq, eps=eps, workspace=workspace)
+    _pool("grn_backward", dtype, "NKB_GRN_BWD_APPLY", g, out, N, HW, C_, in2=u, weight=weight, sumsq=sumsq, mul=mul, eps=eps,
+          workspace=workspace)
+    if dweight is not None or dbias is not None:
+        grn_param(dtype, sumsq, dweight, dbias, N, HW, C_, workspace, eps=eps)
+
+
+def grn_param(dtype, sumsq, dweight, dbias, N, HW, C_, workspace, eps=1e-6):
+    """dweight / dbias += their sums over the images, from the tables grn_backward left in `workspace`."""
+    _pool("grn_param", dtype, "NKB_GRN_PARAM", None, None, N, HW, C_, sumsq=sumsq, dweight=dweight, dbias=dbias, eps=eps,
+          workspace=workspace)
 
 
 def stem_pack(dtype, x, out, N, C_, H, W):

@@ -1546,6 +1546,32 @@ class HipEngine:
         hip.layer_scale(self.d, True, z, g, self.arena.param_flat(gamma), gz, M, C, dgamma=self.arena.grad_flat(gamma), workspace=work)
         return gz
 
+    def grn(self, key: str, u: torch.Tensor, grn_module, N: int, HW: int, train: bool) -> torch.Tensor:
+        """Global response normalisation of the ConvNeXt V2 MLP (csrc/grn.hip) over [N*HW, Ch] rows: two launches, the per-image
+        sums of squares [N, Ch] (fp32) and the apply pass.  Train mode keeps u and the sums for backward; eval mode keeps nothing."""
+        M, Ch = u.shape
+        a = self.arena
+        out = self.ws.get(key + ".y", (M, Ch), self.T)
+        sumsq = self.ws.get(key + ".sumsq", (N, Ch), torch.float32)
+        hip.grn(self.d, u, a.param_flat(grn_module.weight), a.param_flat(grn_module.bias), out, sumsq, N, HW, Ch, eps=grn_module.eps)
+        if train:
+            self.saved[key] = dict(u=u, sumsq=sumsq, grn=grn_module, geom=(N, HW, Ch))
+        return out
+
+    def grn_backward(self, key: str, g: torch.Tensor, slot: str, mul: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """du = (g s + u t) (* mul: the activation derivative the fc1 epilogue kept, so GELU backward is the same pass) on the main
+        stream: a reduce launch (P = sum_p g u, Q = sum_p g) and the apply launch; dweight / dbias from those tables on the side
+        stream, "+=" into the arena.  The tables live in the block's scratch set (begin_block), which the main stream does not
+        reuse before the side stream has read them."""
+        sv = self.saved[key]
+        u, sumsq, mod, (N, HW, Ch) = sv["u"], sv["sumsq"], sv["grn"], sv["geom"]
+        a = self.arena
+        work = self.ws.at_least("grn.tables" + self._suffix, hip.grn_workspace(N, HW, Ch), torch.float32)
+        du = self.scratch(slot, (N * HW, Ch))
+        hip.grn_backward(self.d, g, u, a.param_flat(mod.weight), sumsq, du, None, None, N, HW, Ch, eps=mod.eps, mul=mul, workspace=work)
+        self.on_side(lambda: hip.grn_param(self.d, sumsq, a.grad_flat(mod.weight), a.grad_flat(mod.bias), N, HW, Ch, work, eps=mod.eps))
+        return du
+
     def conv_bias(self, key: str, x: torch.Tensor, conv: nn.Conv2d, train: bool) -> torch.Tensor:
         """Plain convolution with bias on the generic implicit-GEMM kernel (the 2x2 / stride-2 downsample of ConvNeXt);
         x: [N,H,W,Cin].  Saved in conv_bn's format, so conv_backward() serves it; the bias gradient is conv_bias_backward's."""

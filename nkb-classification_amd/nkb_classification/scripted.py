@@ -257,14 +257,54 @@ class _CNBlock(nn.Module):
         return x + y * self.gamma.reshape(1, -1, 1, 1)
 
 
+class _GRN(nn.Module):
+    """timm GlobalResponseNorm over [N, H, W, C] (ConvNeXt V2): x + bias + weight * x * G / (mean_c G + eps), G the L2 norm of a
+    channel over the pixels of one image."""
+
+    def __init__(self, dim: int):
+        super().__init__()
+        self.weight = nn.Parameter(torch.zeros(dim))
+        self.bias = nn.Parameter(torch.zeros(dim))
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        g = torch.sqrt((x * x).sum(dim=[1, 2], keepdim=True))
+        n = g / (g.mean(dim=-1, keepdim=True) + 1e-6)
+        return x + (self.bias + self.weight * (x * n))
+
+
+class _GRNMlp(nn.Module):
+    def __init__(self, dim: int, hidden: int):
+        super().__init__()
+        self.fc1 = nn.Linear(dim, hidden)
+        self.grn = _GRN(hidden)
+        self.fc2 = nn.Linear(hidden, dim)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.fc2(self.grn(torch.nn.functional.gelu(self.fc1(x))))
+
+
+class _CNBlockV2(nn.Module):
+    """ConvNeXt V2 block: GRN inside the MLP, no layer scale."""
+
+    def __init__(self, dim: int):
+        super().__init__()
+        self.conv_dw = nn.Conv2d(dim, dim, 7, padding=3, groups=dim)
+        self.norm = nn.LayerNorm(dim, eps=1e-6)
+        self.mlp = _GRNMlp(dim, 4 * dim)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        y = self.conv_dw(x).permute(0, 2, 3, 1)
+        return x + self.mlp(self.norm(y)).permute(0, 3, 1, 2)
+
+
 class _CNStage(nn.Module):
-    def __init__(self, in_dim: int, dim: int, depth: int, downsample: bool):
+    def __init__(self, in_dim: int, dim: int, depth: int, downsample: bool, use_grn: bool = False):
         super().__init__()
         if downsample:
             self.downsample = nn.Sequential(_CNLayerNorm2d(in_dim, eps=1e-6), nn.Conv2d(in_dim, dim, 2, 2))
         else:
             self.downsample = nn.Identity()
-        self.blocks = nn.Sequential(*[_CNBlock(dim) for _ in range(depth)])
+        self.blocks = nn.Sequential(*[_CNBlockV2(dim) if use_grn else _CNBlock(dim) for _ in range(depth)])
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         return self.blocks(self.downsample(x))
@@ -281,13 +321,13 @@ class _CNHead(nn.Module):
 
 class _ConvNeXt(nn.Module):
     """timm ConvNeXt layout, restated from memory, parity unpinned (see nkb_classification/convnext.py); dropout is the
-    identity at inference, so the nn.Dropout children (parameter-free) are left out."""
+    identity at inference, so the nn.Dropout children (parameter-free) are left out.  use_grn: the V2 members (GRN in the MLP, no gamma)."""
 
-    def __init__(self, depths: List[int], dims: List[int]):
+    def __init__(self, depths: List[int], dims: List[int], use_grn: bool = False):
         super().__init__()
         self.num_features = dims[-1]
         self.stem = nn.Sequential(nn.Conv2d(3, dims[0], 4, 4), _CNLayerNorm2d(dims[0], eps=1e-6))
-        self.stages = nn.Sequential(*[_CNStage(dims[max(i - 1, 0)], dims[i], depths[i], i > 0) for i in range(len(dims))])
+        self.stages = nn.Sequential(*[_CNStage(dims[max(i - 1, 0)], dims[i], depths[i], i > 0, use_grn) for i in range(len(dims))])
         self.head = _CNHead(dims[-1])
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -327,7 +367,7 @@ def _backbone_like(hip_backbone) -> nn.Module:
                     pre_norm=hip_backbone.pre_norm, ln_eps=hip_backbone.ln_eps, init_values=hip_backbone.init_values,
                     no_embed_class=hip_backbone.no_embed_class, act=getattr(hip_backbone, "act", "gelu"))
     if getattr(hip_backbone, "family", "") == "convnext":
-        return _ConvNeXt(list(hip_backbone.depths), list(hip_backbone.dims))
+        return _ConvNeXt(list(hip_backbone.depths), list(hip_backbone.dims), bool(getattr(hip_backbone, "use_grn", False)))
     layers = [len(getattr(hip_backbone, f"layer{i}")) for i in (1, 2, 3, 4)]
     bottleneck = hasattr(getattr(hip_backbone, "layer1")[0], "conv3")
     stem = None
