@@ -264,6 +264,42 @@ enum NkbPoolMode {
     NKB_GRN_BWD_APPLY = 5,
     NKB_GRN_PARAM = 6
 };
+/* Channel attention of the SE / ECA members of the ResNet family (timm SEModule / EcaModule between a block's closing BatchNorm and its
+ * residual add; csrc/se.hip): further modes of nkb_avgpool, in an enum of their own.  c [N][HW][C] is the RAW output of the closing
+ * convolution, bnvec = fp32 [4][C] rows scale, shift, mean, invstd of its BatchNorm (NULL in eval mode: c is the normalised map, scale 1,
+ * shift 0), y = c scale + shift is never written.  C a multiple of 64 up to 2048, N * HW * C < 2^31, rd a multiple of 8 up to 128, k odd
+ * up to 9; all sums, gates, excitation weights and their gradients fp32, in an order that depends on the shape alone.  Every mode takes
+ * `workspace`, the fp32 block of the closing stage: six [N][C] tables cm, s, A, B, dz, ds, two [C] vectors S1, S2, C / 4 floats of
+ * per-workgroup partial sums, then two [N][rd] tables h, dh: workspace_floats >= 6 N C + 2 C + C / 4 + 2 N rd (rd = 0 outside the two
+ * SE gate modes).  The gate modes act on [N][C] and read rd (SE) /
+ * k (ECA) from the HW argument.  The ReLU bits (layout of nkb_bn_apply's relu_bits) travel in the `sumsq` slot.  eps is unused.
+ *   NKB_SE_POOL        cm[b][ch] = mean_p c                                                                   (in = c)
+ *   NKB_SE_GATE        z = scale cm + shift, h = relu(W1 z + b1), s = sigmoid(W2 h + b2)        (in = W1 [rd][C], in2 = W2 [C][rd], bias = b1,
+ *                                                                                                 mul = b2, weight = bnvec; all fp32)
+ *   NKB_ECA_GATE       s[ch] = sigmoid(sum_j w[j] z[ch + j - (k-1)/2]), zero padded                           (in = w [k] fp32, weight = bnvec)
+ *   NKB_SE_FWD_APPLY   out = relu(y s[b] + r), r = in2, or rnd(in2 rscale + rshift) as in nkb_bn_apply; writes the bits when given
+ *                                                                (in = c, in2 = shortcut, weight = bnvec, bias = [rscale | rshift] or NULL)
+ *   NKB_SE_BWD_REDUCE  gm = g under the bits: A[b] = sum_p gm, B[b] = sum_p gm c                              (in = g, in2 = c)
+ *   NKB_SE_BWD_GATE    ds = (scale B + shift A) s (1 - s), dW2 += ds^T h, db2 += sum_b ds, dh = (ds W2) [h > 0], dW1 += dh^T z,
+ *                      db1 += sum_b dh, dz = dh W1, S1 = sum_b (s A + dz), S2 = sum_b (s (B - mean A) + dz (cm - mean))
+ *                                       (in = W1, in2 = W2, weight = bnvec, out = dW1, sumsq = db1, dweight = dW2, dbias = db2; the four
+ *                                        gradients may all be NULL)
+ *   NKB_ECA_BWD_GATE   the same with dw[j] += sum_{b,ch} ds[b][ch] z[b][ch + j - pad], dz[ch] = sum_j w[j] ds[ch - j + pad]
+ *                                                                                       (in = w, weight = bnvec, dweight = dw or NULL)
+ *   NKB_SE_BWD_APPLY   out = dc = scale (gm s[b] + dz[b] / HW - S1 / M - (c - mean) invstd^2 S2 / M), M = N HW;
+ *                      dgamma += invstd S2, dbeta += S1              (in = g, in2 = c, weight = bnvec, dweight = dgamma, dbias = dbeta, may be NULL)
+ * The shortcut's own gradient is gm: its consumers apply the bits themselves, as behind nkb_bn_apply.  Profiles account the pool under
+ * avgpool, the applies under bn_apply / bn_bwd_apply, the backward reduction under bn_bwd_reduce and the gates under misc. */
+enum NkbSeMode {
+    NKB_SE_POOL = 16,
+    NKB_SE_GATE = 17,
+    NKB_ECA_GATE = 18,
+    NKB_SE_FWD_APPLY = 19,
+    NKB_SE_BWD_REDUCE = 20,
+    NKB_SE_BWD_GATE = 21,
+    NKB_ECA_BWD_GATE = 22,
+    NKB_SE_BWD_APPLY = 23
+};
 int nkb_avgpool(int dtype, int mode, const void* in, void* out, int N, int HW, int C, const void* in2, const float* weight,
                 const float* bias, float* sumsq, float* dweight, float* dbias, const void* mul, float eps, float* workspace,
                 long long workspace_floats, nkb_stream_t stream);

@@ -196,6 +196,10 @@ int nkb_grn(int dtype, int mode, const void* in, void* out, int N, int HW, int C
             float* sumsq, float* dweight, float* dbias, const void* mul, float eps, float* workspace, long long workspace_floats,
             hipStream_t stream);
 
+// the channel-attention passes of nkb_avgpool (csrc/se.hip): modes NKB_SE_* / NKB_ECA_* of include/nkbhip.h
+int nkb_se(int dtype, int mode, const void* in, void* out, int N, int HW, int C, const void* in2, const float* weight, const float* bias,
+           float* sumsq, float* dweight, float* dbias, const void* mul, float* workspace, long long workspace_floats, hipStream_t stream);
+
 // bumps a launch counter of nkb_kernel_launches (api.hip); which: an NkbLaunchCounter of include/nkbhip.h
 void nkb_count_launch(int which);
 

@@ -673,6 +673,8 @@ __global__ void avgpool_bwd_kernel(const T* __restrict__ g, T* __restrict__ dx, 
 extern "C" int nkb_avgpool(int dtype, int mode, const void* in, void* out, int N, int HW, int C, const void* in2, const float* weight,
                            const float* bias, float* sumsq, float* dweight, float* dbias, const void* mul, float eps, float* workspace,
                            long long workspace_floats, hipStream_t stream) {
+    if (mode >= NKB_SE_POOL && mode <= NKB_SE_BWD_APPLY)
+        return nkb_se(dtype, mode, in, out, N, HW, C, in2, weight, bias, sumsq, dweight, dbias, mul, workspace, workspace_floats, stream);
     if (mode < NKB_POOL_AVG_FWD || mode > NKB_GRN_PARAM) { nkb_set_error("avgpool: bad mode %d", mode); return 1; }
     if (mode >= NKB_GRN_FWD_REDUCE)
         return nkb_grn(dtype, mode, in, out, N, HW, C, in2, weight, bias, sumsq, dweight, dbias, mul, eps, workspace, workspace_floats, stream);

@@ -8,6 +8,7 @@ HipEngine through libnkbhip, never by torch.nn forward methods.
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence
 
 import torch
@@ -41,15 +42,46 @@ def transformer_layer_groups(backbone: nn.Module) -> List[List[nn.Parameter]]:
     return groups
 
 
+def _make_divisible(v: float, divisor: int = 8) -> int:
+    return max(divisor, int(v + divisor / 2) // divisor * divisor)
+
+
+class _SE(_ParamOnly):
+    """timm SEModule: fc1 = Conv2d(C, rd, 1), ReLU, fc2 = Conv2d(rd, C, 1), sigmoid, on the spatial mean; rd = make_divisible(C / 16, 8)."""
+    kind = "se"
+
+    def __init__(self, channels: int):
+        super().__init__()
+        rd = _make_divisible(channels / 16, 8)
+        self.fc1 = nn.Conv2d(channels, rd, 1, bias=True)
+        self.fc2 = nn.Conv2d(rd, channels, 1, bias=True)
+
+
+class _ECA(_ParamOnly):
+    """timm EcaModule: one Conv1d(1, 1, k, zero padding (k - 1) / 2, no bias) along the channel axis of the pooled vector, sigmoid."""
+    kind = "eca"
+
+    def __init__(self, channels: int):
+        super().__init__()
+        t = int(abs(math.log2(channels) + 1) / 2)
+        k = max(t if t % 2 else t + 1, 3)
+        self.conv = nn.Conv1d(1, 1, k, padding=(k - 1) // 2, bias=False)
+
+
+_ATTN = {"se": _SE, "eca": _ECA}
+
+
 class _Basic(_ParamOnly):
     expansion = 1
 
-    def __init__(self, inplanes, planes, stride, downsample):
+    def __init__(self, inplanes, planes, stride, downsample, attn=None):
         super().__init__()
         self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(planes)
         self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False)
         self.bn2 = nn.BatchNorm2d(planes)
+        if attn is not None:                       # registered between the last BatchNorm and downsample: keys bn2.*, se.*, downsample.*
+            self.se = _ATTN[attn](planes)
         self.downsample = downsample
 
     def stages(self):
@@ -62,7 +94,7 @@ class _Basic(_ParamOnly):
 class _Bottle(_ParamOnly):
     expansion = 4
 
-    def __init__(self, inplanes, planes, stride, downsample):
+    def __init__(self, inplanes, planes, stride, downsample, attn=None):
         super().__init__()
         self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(planes)
@@ -70,6 +102,8 @@ class _Bottle(_ParamOnly):
         self.bn2 = nn.BatchNorm2d(planes)
         self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * 4)
+        if attn is not None:                       # keys bn3.*, se.*, downsample.*
+            self.se = _ATTN[attn](planes * 4)
         self.downsample = downsample
 
     def stages(self):
@@ -90,12 +124,18 @@ class HipResNet(_ParamOnly):
       avg_down       projection shortcut = Sequential(AvgPool2d(2, 2, ceil_mode=True, count_include_pad=False) in a stride-2 block /
                      Identity in a stride-1 block, Conv 1x1 stride 1, BN): keys downsample.1.weight, downsample.2.* (index 0 holds
                      no parameters).
-    The second and third stem convolution run on csrc/stem3.hip, the pool on nkb_avgpool2x2; everything else is the plain members' path."""
+    The second and third stem convolution run on csrc/stem3.hip, the pool on nkb_avgpool2x2; everything else is the plain members' path.
+
+    The SE / ECA members (seresnet*, ecaresnet*; attn="se" / "eca") put timm's channel attention between the closing BatchNorm of every
+    block and the residual add: the block gains an attribute `se` registered after the last BatchNorm and before `downsample` (keys
+    ... bn3.*, se.fc1.{weight,bias}, se.fc2.{weight,bias}, downsample.* for SE with 4-D 1x1 Conv2d weights and rd = make_divisible(C / 16,
+    8); se.conv.weight [1][1][k] for ECA), forward act(se(bn_last(conv_last(.))) + shortcut).  Restated from memory of timm as well: parity
+    unpinned.  The attention weights are fp32 masters read by csrc/se.hip: no bf16 shadow, no data-gradient filter, not in gemm_convs()."""
 
     family = "resnet"
 
     def __init__(self, block, layers: Sequence[int], zero_init_last: bool = True, stem: Optional[Sequence[int]] = None,
-                 avg_down: bool = False):
+                 avg_down: bool = False, attn: Optional[str] = None):
         super().__init__()
         self.deep_stem, self.avg_down = stem is not None, avg_down
         if stem is None:
@@ -120,12 +160,12 @@ class HipResNet(_ParamOnly):
                 elif s != 1 or inplanes != planes * block.expansion:
                     down = nn.Sequential(nn.Conv2d(inplanes, planes * block.expansion, 1, s, bias=False),
                                          nn.BatchNorm2d(planes * block.expansion))
-                blocks.append(block(inplanes, planes, s, down))
+                blocks.append(block(inplanes, planes, s, down, attn) if attn is not None else block(inplanes, planes, s, down))
                 inplanes = planes * block.expansion
             setattr(self, f"layer{i + 1}", nn.Sequential(*blocks))
         self.num_features = inplanes
         for m in self.modules():
-            if isinstance(m, nn.Conv2d):
+            if isinstance(m, nn.Conv2d):           # (the SE excitation's 1x1 convolutions included; their biases and ECA's Conv1d keep torch's default)
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
         if zero_init_last:
             for m in self.modules():
@@ -198,7 +238,8 @@ class HipResNet(_ParamOnly):
             # the Gram form's backward needs the masked output gradient WITH its sums from the next block's first data gradient
             # (HipEngine.can_fuse_residual_bn_backward): decide on that producer here, where the forward form is chosen — a next
             # block whose first convolution takes the parity-class data gradient (3x3 / stride 2) cannot supply them
-            want_gram = (isinstance(blk, _Bottle) and bi + 1 < nblocks and train
+            se = getattr(blk, "se", None)          # channel attention: its own closing stage, never the Gram form
+            want_gram = (isinstance(blk, _Bottle) and bi + 1 < nblocks and train and se is None
                          and not eng.s2_classes(all_blocks[bi + 1][1].stages()[0][0]))
             proj = None
             dpool, dconv, dbn = self.shortcut(blk) if blk.downsample is not None else (None, None, None)
@@ -227,6 +268,9 @@ class HipResNet(_ParamOnly):
             gram = want_gram and eng.can_fuse_bn_backward(f"{name}.{len(stages) - 2}")
             if proj is not None and not gram:
                 raise RuntimeError(f"{name}: projection shortcut planned into a Gram-form closing stage that did not qualify")
+            if se is not None:
+                x = eng.conv_bn_se(f"{name}.{len(stages) - 1}", x, cv, bn, se, short, short_affine, train)
+                continue
             x = eng.conv_bn(f"{name}.{len(stages) - 1}", x, cv, bn, True, short, train, res_affine=short_affine, gram=gram, proj=proj)
         return eng.avgpool("gap", x)
 
@@ -254,6 +298,10 @@ class HipResNet(_ParamOnly):
                 gc = eng.bn_backward_fused(prev, ga, st, f"c{n - 1}")
                 bits = None
                 top = n - 2
+            elif eng.saved[last].get("se") is not None:
+                assert g_stats is None             # (can_fuse_residual_bn_backward: g arrives unmasked and un-reduced)
+                gc = eng.se_closing_backward(last, g, "t0")
+                bits = eng.saved[last]["bits"]
             elif g_stats is not None:
                 gc = eng.bn_backward_fused(last, g, g_stats, "t0")
                 bits = None                              # g is masked already
@@ -331,6 +379,25 @@ _RESNETS = {
     "resnet_tiny_bottleneck": (_Bottle, (1, 1, 1, 1)),
 }
 
+# the SE / ECA siblings: the same blocks with channel attention in front of the residual add (csrc/se.hip)
+_SE_RESNETS = {
+    "seresnet18": (_Basic, (2, 2, 2, 2), dict(attn="se")),
+    "seresnet34": (_Basic, (3, 4, 6, 3), dict(attn="se")),
+    "seresnet50": (_Bottle, (3, 4, 6, 3), dict(attn="se")),
+    "seresnet101": (_Bottle, (3, 4, 23, 3), dict(attn="se")),
+    "seresnet152": (_Bottle, (3, 8, 36, 3), dict(attn="se")),
+    "seresnet50t": (_Bottle, (3, 4, 6, 3), dict(attn="se", stem=(24, 32), avg_down=True)),
+    "seresnet152d": (_Bottle, (3, 8, 36, 3), dict(attn="se", stem=(32, 32), avg_down=True)),
+    "ecaresnet26t": (_Bottle, (2, 2, 2, 2), dict(attn="eca", stem=(24, 32), avg_down=True)),
+    "ecaresnet50t": (_Bottle, (3, 4, 6, 3), dict(attn="eca", stem=(24, 32), avg_down=True)),
+    "ecaresnet50d": (_Bottle, (3, 4, 6, 3), dict(attn="eca", stem=(32, 32), avg_down=True)),
+    "ecaresnet101d": (_Bottle, (3, 4, 23, 3), dict(attn="eca", stem=(32, 32), avg_down=True)),
+    # reduced members for the fast tests
+    "seresnet_tiny_basic": (_Basic, (1, 1, 1, 1), dict(attn="se")),
+    "seresnet_tiny_bottleneck": (_Bottle, (1, 1, 1, 1), dict(attn="se")),
+    "ecaresnet_tiny_bottleneck": (_Bottle, (1, 1, 1, 1), dict(attn="eca")),
+}
+
 
 def create_backbone(name: str, pretrained: bool = False) -> nn.Module:
     """Counterpart of timm.create_model(name, pretrained=..., num_classes=0) for the families this engine runs."""
@@ -338,8 +405,8 @@ def create_backbone(name: str, pretrained: bool = False) -> nn.Module:
     if pretrained:
         raise RuntimeError(f"pretrained=True needs timm's weight hub, which this offline engine does not ship; "
                            f"load a timm-format state_dict through cfg.model['checkpoint'] instead ({name})")
-    if key in _RESNETS:
-        blk, layers, *extra = _RESNETS[key]
+    if key in _RESNETS or key in _SE_RESNETS:
+        blk, layers, *extra = _RESNETS[key] if key in _RESNETS else _SE_RESNETS[key]
         return HipResNet(blk, layers, **(extra[0] if extra else {}))
     from .vit import create_vit, vit_members
     m = create_vit(key)
@@ -347,6 +414,7 @@ def create_backbone(name: str, pretrained: bool = False) -> nn.Module:
         from .convnext import _CONVNEXTS, create_convnext
         m = create_convnext(key)
     if m is None:
+        se_members = sorted(k for k in _SE_RESNETS if "_tiny_" not in k)
         raise NotImplementedError(f"backbone {name!r} is not implemented by the HIP engine "
-                                  f"(available: {sorted(_RESNETS)} + {vit_members()} + {sorted(_CONVNEXTS)})")
+                                  f"(available: {sorted(_RESNETS)} + {se_members} + {vit_members()} + {sorted(_CONVNEXTS)})")
     return m

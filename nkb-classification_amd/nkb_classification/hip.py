@@ -612,6 +612,50 @@ def grn_param(dtype, sumsq, dweight, dbias, N, HW, C_, workspace, eps=1e-6):
           workspace=workspace)
 
 
+# enum NkbSeMode of the header: the channel-attention passes of nkb_avgpool ({"NKB_SE_POOL": 16, ..., "NKB_SE_BWD_APPLY": 23})
+_SE_MODES = cabi.parse_enum(_HEADER, "NkbSeMode")
+
+
+def se_workspace(N, C_, rd=0) -> int:
+    """Floats of the fp32 block one SE / ECA closing stage keeps (include/nkbhip.h, NkbSeMode): six [N][C] tables cm, s, A, B, dz, ds,
+    the vectors S1, S2 [C], C / 4 floats of per-workgroup partial sums, then h, dh [N][rd] (rd = 0 for ECA).  cm, s and h live from
+    forward to backward."""
+    return 6 * N * C_ + 2 * C_ + C_ // 4 + 2 * N * rd
+
+
+def _se(what, dtype, mode, N, hw, C_, workspace, src=None, dst=None, in2=None, weight=None, bias=None, sumsq=None, dweight=None,
+        dbias=None, mul=None):
+    check(load().nkb_avgpool(dtype, _SE_MODES[mode], ptr(src), ptr(dst), N, hw, C_, ptr(in2), ptr(weight), ptr(bias), ptr(sumsq),
+                             ptr(dweight), ptr(dbias), ptr(mul), 0.0, ptr(workspace), workspace.numel() if workspace is not None else 0,
+                             stream()), what)
+
+
+def se_forward(dtype, c, short, out, bnvec, workspace, N, HW, C_, w1, b1=None, w2=None, b2=None, bits=None, res_bnvec=None):
+    """out = relu((c scale + shift) s[b] + shortcut) in three launches: pool, gate, apply.  w2 is None: ECA with the taps w1, else SE
+    (w1 [rd][C], b1, w2 [C][rd], b2, fp32 masters).  bnvec None: eval form on a normalised c.  res_bnvec: the shortcut is a raw
+    projection output with these [scale | shift | ...] rows."""
+    _se("se_pool", dtype, "NKB_SE_POOL", N, HW, C_, workspace, src=c)
+    if w2 is None:
+        _se("eca_gate", dtype, "NKB_ECA_GATE", N, w1.numel(), C_, workspace, src=w1, weight=bnvec)
+    else:
+        _se("se_gate", dtype, "NKB_SE_GATE", N, w1.shape[0], C_, workspace, src=w1, in2=w2, bias=b1, mul=b2, weight=bnvec)
+    _se("se_apply", dtype, "NKB_SE_FWD_APPLY", N, HW, C_, workspace, src=c, dst=out, in2=short, weight=bnvec, bias=res_bnvec, sumsq=bits)
+
+
+def se_backward(dtype, g, c, bits, dc, bnvec, workspace, N, HW, C_, w1, w2=None, dw1=None, db1=None, dw2=None, db2=None, dgamma=None,
+                dbeta=None):
+    """dc = gradient of the raw closing-convolution output from g, the (unmasked) gradient of the block output, in three launches:
+    reduce, gate, apply.  The parameter gradients accumulate (+=); the workspace is the one se_forward filled."""
+    _se("se_bwd_reduce", dtype, "NKB_SE_BWD_REDUCE", N, HW, C_, workspace, src=g, in2=c, sumsq=bits)
+    if w2 is None:
+        _se("eca_bwd_gate", dtype, "NKB_ECA_BWD_GATE", N, w1.numel(), C_, workspace, src=w1, weight=bnvec, dweight=dw1)
+    else:
+        _se("se_bwd_gate", dtype, "NKB_SE_BWD_GATE", N, w1.shape[0], C_, workspace, src=w1, in2=w2, weight=bnvec, dst=dw1, sumsq=db1,
+            dweight=dw2, dbias=db2)
+    _se("se_bwd_apply", dtype, "NKB_SE_BWD_APPLY", N, HW, C_, workspace, src=g, dst=dc, in2=c, weight=bnvec, sumsq=bits, dweight=dgamma,
+        dbias=dbeta)
+
+
 def stem_pack(dtype, x, out, N, C_, H, W):
     check(load().nkb_stem_pack(dtype, ptr(x), ptr(out), N, C_, H, W, stream()), "stem_pack")
 

@@ -457,6 +457,56 @@ class HipEngine:
                          res_scale=res_affine[0] if res_affine else None, res_shift=res_affine[1] if res_affine else None)
         return y, bits
 
+    @staticmethod
+    def _se_weights(se):
+        """(w1, b1, w2, b2) of timm's SEModule, or (taps, None, None, None) of its EcaModule: fp32 masters, read by csrc/se.hip as they are."""
+        if hasattr(se, "fc1"):
+            return se.fc1.weight, se.fc1.bias, se.fc2.weight, se.fc2.bias
+        return se.conv.weight, None, None, None
+
+    def conv_bn_se(self, key: str, x: torch.Tensor, conv: nn.Conv2d, bn: nn.BatchNorm2d, se, short: torch.Tensor, res_affine, train: bool):
+        """Closing stage of an SE / ECA block: out = relu(se(bn(conv(x))) + shortcut).  The convolution and its statistics are conv_bn's
+        (defer_apply); then one reduction read of the raw output c (per-image channel means), the tiny gate launch and one apply pass
+        that reads c and the shortcut and writes out and the ReLU bits: bn(c) is never written.  Eval: the folded convolution delivers
+        the normalised map, the same three passes run without BatchNorm vectors and nothing is saved."""
+        c, scale, _ = self.conv_bn(key, x, conv, bn, False, None, train, defer_apply=True)
+        N, P, Q, co = c.shape
+        a = self.arena
+        w1, b1, w2, b2 = self._se_weights(se)
+        pf = lambda p: a.param_flat(p) if p is not None else None       # noqa: E731
+        rd = w1.shape[0] if w2 is not None else 0
+        work = self.ws.get(key + ".se", (hip.se_workspace(N, co, rd),), torch.float32)
+        bnvec = self.ws.get(key + ".bnvec", (4, co), torch.float32) if scale is not None else None
+        rvec = None
+        if res_affine is not None:
+            rvec = res_affine[0]
+            assert res_affine[1].data_ptr() == rvec.data_ptr() + 4 * co          # rows scale, shift of the shortcut's bnvec
+        out = self.ws.get(key + (".y" if train else ".sey"), (N, P, Q, co), self.T)
+        bits = self.ws.get(key + ".bits", (N * P * Q, co // (8 if self.T == torch.bfloat16 else 4)), torch.uint8) if train else None
+        w1f = pf(w1).view(rd, co) if rd else pf(w1)
+        hip.se_forward(self.d, c, short, out, bnvec, work, N, P * Q, co, w1f, pf(b1), pf(w2), pf(b2), bits=bits, res_bnvec=rvec)
+        if train:
+            self.saved[key].update(y=out, bits=bits, has_res=True, se=dict(module=se, work=work, bnvec=bnvec))
+        return out
+
+    def se_closing_backward(self, key: str, g: torch.Tensor, slot: str) -> torch.Tensor:
+        """Backward of conv_bn_se's tail.  g: UNMASKED gradient of the block output (the shortcut's consumers apply saved["bits"]
+        themselves).  One reduce pass (g, c, bits), the gate's backward with every parameter gradient of the attention module, and one
+        apply pass that writes the gradient of the raw conv output, BatchNorm backward included (its sums follow from the per-image
+        sums).  Returns that gradient for conv_backward(key, ...)."""
+        sv = self.saved[key]
+        st, bn, c = sv["se"], sv["bn"], sv["c"]
+        N, P, Q, co = c.shape
+        a = self.arena
+        w1, b1, w2, b2 = self._se_weights(st["module"])
+        gf = lambda p: a.grad_flat(p) if p is not None else None        # noqa: E731
+        dc = self.scratch(slot, c.shape)
+        w1f = a.param_flat(w1).view(w1.shape[0], co) if w2 is not None else a.param_flat(w1)
+        hip.se_backward(self.d, g, c, sv["bits"], dc, st["bnvec"], st["work"], N, P * Q, co, w1f,
+                        a.param_flat(w2) if w2 is not None else None, dw1=gf(w1), db1=gf(b1), dw2=gf(w2), db2=gf(b2),
+                        dgamma=a.grad_flat(bn.weight), dbeta=a.grad_flat(bn.bias))
+        return dc
+
     def gram_ok(self, conv, res, x) -> bool:
         """The Gram form exists for bf16 1x1 / stride-1 closing stages with 64 | Cin <= 512 and Cout > 64 (every timm Bottleneck conv3);
         it is TAKEN up to Cin = 128 (_GRAM_MAX_C; ResNet-50 layer1 / layer2, 7 of 16 blocks, 73 % of the closing-stage bytes): the small
@@ -842,6 +892,8 @@ class HipEngine:
         """The stage `bn_key` closes a residual block (kept ReLU bits) and `consumer_key` is the first conv of the next
         block, whose data gradient (+ shortcut gradient) IS the gradient of that stage's output."""
         sv, cv = self.saved[bn_key], self.saved[consumer_key]
+        if sv.get("se") is not None:      # an SE / ECA closing stage reduces the UNMASKED gradient itself (se_closing_backward)
+            return False
         return (sv.get("bits") is not None and sv["y"].shape[-1] % 8 == 0
                 and not self.s2_classes(cv["conv"]) and not cv["col_input"] and not cv["stem_packed"])
 

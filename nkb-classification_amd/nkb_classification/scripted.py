@@ -10,29 +10,67 @@ kernels on any device.  It is an export artefact only — never used by `train_e
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional
 
 import torch
 from torch import nn
 
 
+class _SEModule(nn.Module):
+    """timm SEModule: x * sigmoid(fc2(relu(fc1(mean over the map)))), rd = make_divisible(C / 16, 8)."""
+
+    def __init__(self, channels: int):
+        super().__init__()
+        rd = max(8, int(channels / 16 + 4) // 8 * 8)
+        self.fc1 = nn.Conv2d(channels, rd, 1, bias=True)
+        self.fc2 = nn.Conv2d(rd, channels, 1, bias=True)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        s = x.mean((2, 3), keepdim=True)
+        return x * torch.sigmoid(self.fc2(torch.relu(self.fc1(s))))
+
+
+class _EcaModule(nn.Module):
+    """timm EcaModule: x * sigmoid(Conv1d(1, 1, k, zero padding) along the channel axis of the pooled vector)."""
+
+    def __init__(self, channels: int):
+        super().__init__()
+        t = int(abs(math.log2(channels) + 1) / 2)
+        k = max(t if t % 2 else t + 1, 3)
+        self.conv = nn.Conv1d(1, 1, k, padding=(k - 1) // 2, bias=False)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        s = x.mean((2, 3)).unsqueeze(1)                       # [N][1][C]
+        return x * torch.sigmoid(self.conv(s)).squeeze(1).unsqueeze(-1).unsqueeze(-1)
+
+
+def _attn_module(attn: Optional[str], channels: int) -> nn.Module:
+    if attn == "se":
+        return _SEModule(channels)
+    if attn == "eca":
+        return _EcaModule(channels)
+    return nn.Identity()
+
+
 class _BasicBlock(nn.Module):
-    def __init__(self, inplanes: int, planes: int, stride: int, downsample: Optional[nn.Module]):
+    def __init__(self, inplanes: int, planes: int, stride: int, downsample: Optional[nn.Module], attn: Optional[str] = None):
         super().__init__()
         self.conv1 = nn.Conv2d(inplanes, planes, 3, stride, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(planes)
         self.conv2 = nn.Conv2d(planes, planes, 3, 1, 1, bias=False)
         self.bn2 = nn.BatchNorm2d(planes)
+        self.se = _attn_module(attn, planes)
         self.downsample = downsample if downsample is not None else nn.Identity()
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         y = torch.relu(self.bn1(self.conv1(x)))
-        y = self.bn2(self.conv2(y))
+        y = self.se(self.bn2(self.conv2(y)))
         return torch.relu(y + self.downsample(x))
 
 
 class _Bottleneck(nn.Module):
-    def __init__(self, inplanes: int, planes: int, stride: int, downsample: Optional[nn.Module]):
+    def __init__(self, inplanes: int, planes: int, stride: int, downsample: Optional[nn.Module], attn: Optional[str] = None):
         super().__init__()
         self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
         self.bn1 = nn.BatchNorm2d(planes)
@@ -40,17 +78,18 @@ class _Bottleneck(nn.Module):
         self.bn2 = nn.BatchNorm2d(planes)
         self.conv3 = nn.Conv2d(planes, planes * 4, 1, bias=False)
         self.bn3 = nn.BatchNorm2d(planes * 4)
+        self.se = _attn_module(attn, planes * 4)
         self.downsample = downsample if downsample is not None else nn.Identity()
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         y = torch.relu(self.bn1(self.conv1(x)))
         y = torch.relu(self.bn2(self.conv2(y)))
-        y = self.bn3(self.conv3(y))
+        y = self.se(self.bn3(self.conv3(y)))
         return torch.relu(y + self.downsample(x))
 
 
 class _ResNet(nn.Module):
-    def __init__(self, bottleneck: bool, layers, stem: Optional[List[int]] = None, avg_down: bool = False):
+    def __init__(self, bottleneck: bool, layers, stem: Optional[List[int]] = None, avg_down: bool = False, attn: Optional[str] = None):
         super().__init__()
         exp = 4 if bottleneck else 1
         block = _Bottleneck if bottleneck else _BasicBlock
@@ -73,7 +112,7 @@ class _ResNet(nn.Module):
                     ds = nn.Sequential(pool, nn.Conv2d(inplanes, planes * exp, 1, 1, bias=False), nn.BatchNorm2d(planes * exp))
                 elif b == 0 and (stride != 1 or inplanes != planes * exp):
                     ds = nn.Sequential(nn.Conv2d(inplanes, planes * exp, 1, stride, bias=False), nn.BatchNorm2d(planes * exp))
-                blocks.append(block(inplanes, planes, stride, ds))
+                blocks.append(block(inplanes, planes, stride, ds, attn))
                 inplanes = planes * exp
             setattr(self, f"layer{li + 1}", nn.Sequential(*blocks))
         self.num_features = inplanes
@@ -373,7 +412,8 @@ def _backbone_like(hip_backbone) -> nn.Module:
     stem = None
     if getattr(hip_backbone, "deep_stem", False):
         stem = [hip_backbone.conv1[0].out_channels, hip_backbone.conv1[3].out_channels]
-    return _ResNet(bottleneck, layers, stem, bool(getattr(hip_backbone, "avg_down", False)))
+    se = getattr(getattr(hip_backbone, "layer1")[0], "se", None)             # the SE / ECA members: channel attention in every block
+    return _ResNet(bottleneck, layers, stem, bool(getattr(hip_backbone, "avg_down", False)), getattr(se, "kind", None))
 
 
 def build_scriptable(hip_model) -> nn.Module:
