@@ -145,7 +145,7 @@ __device__ __forceinline__ void bn_finalize_body(const PT* __restrict__ partials
     const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
     scale[c] = g * invstd;
     shift[c] = b - mean * g * invstd;
-    if (save_mean) { save_mean[c] = mean; save_invstd[c] = invstd; }
+    if (training && save_mean) { save_mean[c] = mean; save_invstd[c] = invstd; }
 }
 template <typename PT>
 __global__ void bn_finalize_kernel(const PT* __restrict__ partials, int tiles, int C, float count,
