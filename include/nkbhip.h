@@ -428,7 +428,9 @@ size_t nkb_layernorm_workspace_floats(int D); /* backward: optional scratch for 
 int nkb_layernorm_param_reduce(float* workspace, int rows, int D, int planes, float* dgamma, float* dbeta, float* colsum,
                                nkb_stream_t stream);
 /* MLP activation, kind = NKB_ACT_GELU (exact erf) or NKB_ACT_QUICK_GELU (any other kind is refused, the message names `kind`):
- * dy == NULL -> out = act(x); else out = dy * act'(x) */
+ * dy == NULL -> out = act(x); else out = dy * act'(x).  An unknown dtype is refused.
+ * Zero extents (rows / B / outer / inner / C == 0) of nkb_layernorm, nkb_attn_softmax, nkb_head_transpose, nkb_vit_assemble,
+ * nkb_colsum2d and nkb_scale_rows are valid calls that return 0 without a launch; negative extents are refused. */
 /* forward that also stores act'(x) (timm Mlp.act, backward then is the act-4 epilogue of nkb_linear_gelu); gp may be x (in place) */
 int nkb_gelu_fwd_dgelu(int dtype, const void* x, void* y, void* gp, long long n, int kind, nkb_stream_t stream);
 int nkb_gelu(int dtype, const void* x, const void* dy, void* out, long long n, int kind, nkb_stream_t stream);

@@ -681,6 +681,8 @@ extern "C" int nkb_layernorm(int dtype, int backward, const void* in, long long 
     if (!yq && (row_scale || colsum)) { nkb_set_error("layernorm: row_scale / colsum belong to the second output"); return 1; }
     if (backward && (dgamma == nullptr) != (dbeta == nullptr)) { nkb_set_error("layernorm: dgamma and dbeta go together"); return 1; }
     if (backward && !dgamma && !workspace) { nkb_set_error("layernorm: partial-rows-only backward needs the workspace"); return 1; }
+    if (rows < 0) { nkb_set_error("layernorm: rows=%d", rows); return 1; }
+    if (rows == 0) return 0;                                  // nothing to normalise and nothing to add: no launch (an empty grid is a launch error)
     NkbProfScope prof(NKB_K_LN, stream, 0);
     int grid = (rows + 3) / 4;
     if (!backward) { if (grid > (yq ? 1024 : 256 * 16)) grid = yq ? 1024 : 256 * 16; }   // (fp8 copy: one amax atomic per block)
@@ -747,6 +749,7 @@ static bool gelu_kind_ok(const char* who, int kind) {
 }
 extern "C" int nkb_gelu(int dtype, const void* x, const void* dy, void* out, long long n, int kind, hipStream_t stream) {
     const int N = dtype == NKB_DT_BF16 ? 8 : 4;
+    if (dtype != NKB_DT_BF16 && dtype != NKB_DT_F32) { nkb_set_error("gelu: bad dtype %d", dtype); return 1; }
     if (!gelu_kind_ok("gelu", kind)) return 1;
     if (n % N) { nkb_set_error("gelu: element count %lld not a multiple of %d", n, N); return 1; }
     NkbProfScope prof(NKB_K_GELU, stream, 0);
@@ -892,6 +895,8 @@ __global__ __launch_bounds__(256) void attn_softmax_kernel(const float* __restri
 }
 extern "C" int nkb_attn_softmax(int dtype, int backward, const float* s, int lds, const void* p_in, void* out, int ldp,
                                 long long rows, int cols, float scale, hipStream_t stream) {
+    if (rows < 0 || cols < 0 || ldp < 0) { nkb_set_error("attn_softmax: rows=%lld, cols=%d, ldp=%d", rows, cols, ldp); return 1; }
+    if (rows == 0 || ldp == 0) return 0;                      // nothing to write: no launch
     NkbProfScope prof(NKB_K_ATTN, stream, 0);
     long long g = (rows + 3) / 4;
     if (g > 256 * 32) g = 256 * 32;
@@ -924,6 +929,11 @@ __global__ void head_transpose_kernel(const T* __restrict__ in, int ld_in, long 
 }
 extern "C" int nkb_head_transpose(int dtype, const void* in, int ld_in, long long sio, long long sii, int outer, int inner,
                                   void* out, int T_, int dh, int ldt, hipStream_t stream) {
+    if (outer < 0 || inner < 0 || T_ < 0 || dh < 0 || ldt < 0) {
+        nkb_set_error("head_transpose: outer=%d, inner=%d, T=%d, dh=%d, ldt=%d", outer, inner, T_, dh, ldt);
+        return 1;
+    }
+    if (outer == 0 || inner == 0 || dh == 0 || ldt == 0) return 0;   // nothing to write: no launch
     NkbProfScope prof(NKB_K_ATTN, stream, 0);
     dim3 grid((ldt + 63) / 64, (dh + 63) / 64, outer * inner);
     if (dtype == NKB_DT_BF16) hipLaunchKernelGGL(head_transpose_kernel<bf16_t>, grid, dim3(256), 0, stream, (const bf16_t*)in, ld_in, sio, sii, inner, (bf16_t*)out, T_, dh, ldt);
@@ -982,6 +992,8 @@ __global__ void vit_assemble_kernel(const T* __restrict__ tok, const float* __re
 }
 extern "C" int nkb_vit_assemble(int dtype, int backward, void* tok, const float* cls, const float* pos, void* x, int B, int Tn,
                                 int D, hipStream_t stream) {
+    if (B < 0 || Tn < 0 || D < 0) { nkb_set_error("vit_assemble: B=%d, Tn=%d, D=%d", B, Tn, D); return 1; }
+    if (B == 0 || Tn == 0 || D == 0) return 0;                // nothing to write: no launch
     NkbProfScope prof(NKB_K_MISC, stream, 0);
     size_t total = (size_t)B * Tn * D, g = (total + 255) / 256;
     if (g > 256 * 16) g = 256 * 16;
@@ -1013,6 +1025,8 @@ __global__ void colsum2d_kernel(const T* __restrict__ x, float* __restrict__ out
 // workspace (optional, >= 256 * C floats): per-row-block partial sums + an ordered second stage instead of float atomics
 extern "C" int nkb_colsum2d(int dtype, const void* x, float* out, long long rows, int C, long long ld, float* workspace,
                             hipStream_t stream) {
+    if (rows < 0 || C < 0) { nkb_set_error("colsum2d: rows=%lld, C=%d", rows, C); return 1; }
+    if (rows == 0 || C == 0) return 0;                        // out += nothing: no launch
     NkbProfScope prof(NKB_K_MISC, stream, 0);
     int ry = (int)((rows + 255) / 256);
     if (ry > 256) ry = 256;
