@@ -488,7 +488,9 @@ int nkb_wfold(int dtype, const float* w, const float* scale, void* dst, int Cout
  * the albumentations stack, configs/singletask_config.py:162-219, and lets engine.py:40's H2D copy move uint8):
  * src [B][Hs][Ws][3] uint8 (device), sizes [B][2] int32 (h, w of the valid top-left region; NULL = Hs x Ws),
  * flags [B] uint8 (bit 0 horizontal, bit 1 vertical flip; NULL = none), out [B][3][Ho][Wo] fp32 (device);
- * mean / stdev: 3 HOST floats each (fractions of 255 as in A.Normalize); fill: pad value in 0..255. */
+ * mean / stdev: 3 HOST floats each (fractions of 255 as in A.Normalize); fill: pad value in 0..255.
+ * out[b][c][y][x] = (P - 255 mean[c]) * (1 / (255 stdev[c])), every operation in fp32.  out needs the alignment of a float only:
+ * the 16-byte stores are taken where Wo % 4 == 0 and out is 16-byte aligned, element stores otherwise. */
 int nkb_image_prep(const unsigned char* src, const int* sizes, const unsigned char* flags, float* out, int B, int Hs, int Ws,
                    int Ho, int Wo, const float* mean, const float* stdev, float fill, nkb_stream_t stream);
 /* out = keep ? in/(1-p) : 0 (+ add); forward draws keep from a hash of (seed, index) and stores it in mask */
@@ -500,7 +502,12 @@ int nkb_colsum2d(int dtype, const void* x, float* out, long long rows, int C, lo
 /* Losses (kind 0: CrossEntropyLoss(weight); kind 1: FocalLoss(alpha, gamma) over un-ignored rows, losses.py:59-94).
  * reduction 0 "mean": out2[0] = loss, out2[1] = 1/normaliser; 1 "sum" / 2 "none": out2[0] = sum, out2[1] = 1 (the per-row
  * losses of "none" are row_state[i].loss, three floats per row).  A label outside [0, C) that is not ignore_index makes the
- * loss NaN (torch asserts on the device there).  probs/argmax double as the logger's softmax/argmax. */
+ * loss NaN (torch asserts on the device there) and its dlogits row NaN.  A batch whose rows are all ignored, or whose class
+ * weights sum to zero, gives loss 0 and factor 0 (F.cross_entropy gives NaN).  Focal 'mean' divides by the number of kept rows.
+ * probs/argmax double as the logger's softmax/argmax (target, row_state and out2 NULL); argmax equals torch.argmax on every row:
+ * the first maximum, a NaN above every number, the first NaN among several, column 0 for a row of -inf.  Any other kind, a
+ * reduction outside 0..2, row_state without target and negative B or C are refused; B == 0 or C == 0 returns 0 without a launch
+ * (backward as well) and writes nothing. */
 int nkb_loss_forward(int kind, const float* logits, int ld, const long long* target, int B, int C,
                      const float* class_weight, float gamma, long long ignore_index, float* probs, int ldp,
                      int* argmax, void* row_state, float* out2, int reduction, nkb_stream_t stream);
@@ -534,6 +541,8 @@ int nkb_bucket_sum_bf16(const void* parts, long long stride, int nparts, float* 
 int nkb_grad_unscale_check(float* g, long long n, const float* scale, float* found_inf, nkb_stream_t stream);
 int nkb_scaler_update(float* scale, int* growth_tracker, float* found_inf, float* last_found_inf, float growth,
                       float backoff, int interval, nkb_stream_t stream);
+/* out[k] = sum of x[i]^2 over offsets[k] <= i < offsets[k + 1] (nseg + 1 device offsets); an empty segment gives 0.  nseg == 0
+ * returns 0 without a launch, a negative nseg is refused. */
 int nkb_segment_sumsq(const float* x, const long long* offsets, int nseg, float* out, nkb_stream_t stream);
 
 /* fp8 path (BASELINE configs[4] "unicom ViT-L/14 ... fp8"; the reference itself has no fp8 mode — engine.py:43-47 is fp16 autocast):

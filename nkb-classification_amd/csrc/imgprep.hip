@@ -8,7 +8,8 @@
 //   P = the (h_b x w_b) image centred in Ho x Wo (top = (Ho - h) / 2, left = (Wo - w) / 2, as PadIfNeeded) over `fill`.
 //
 // HBM-bound: 3 B read + 12 B written per output pixel.  One thread = 4 consecutive x of one row, all three channels:
-// 12 source bytes (byte loads; neighbouring lanes cover neighbouring bytes) and three 16-byte stores, one per plane.
+// 12 source bytes (byte loads; neighbouring lanes cover neighbouring bytes) and three 16-byte stores, one per plane, where
+// Wo % 4 == 0 and `out` is 16-byte aligned (every row of every plane then is); element stores otherwise.
 #include "common.h"
 
 namespace {
@@ -16,7 +17,7 @@ namespace {
 __global__ __launch_bounds__(256) void image_prep_kernel(const unsigned char* __restrict__ src, const int* __restrict__ sizes,
                                                          const unsigned char* __restrict__ flags, float* __restrict__ out,
                                                          int B, int Hs, int Ws, int Ho, int Wo, float m0, float m1, float m2,
-                                                         float r0, float r1, float r2, float fill) {
+                                                         float r0, float r1, float r2, float fill, bool vec) {
     const int xg = (Wo + 3) >> 2;                       // 4-pixel groups per row
     const long long total = (long long)B * Ho * xg;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(256) void image_prep_kernel(const unsigned char* __
         }
         const size_t plane = (size_t)Ho * Wo;
         float* o = out + (size_t)b * 3 * plane + (size_t)y * Wo + gx * 4;
-        if ((Wo & 3) == 0) {
+        if (vec) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) *(f32x4*)(o + c * plane) = (f32x4){v[c][0], v[c][1], v[c][2], v[c][3]};
         } else {
@@ -76,6 +77,6 @@ extern "C" int nkb_image_prep(const unsigned char* src, const int* sizes, const 
     long long g = (total + 255) / 256;
     if (g > 256 * 32) g = 256 * 32;
     hipLaunchKernelGGL(image_prep_kernel, dim3((unsigned)g), dim3(256), 0, stream, src, sizes, flags, out, B, Hs, Ws, Ho, Wo,
-                       m0, m1, m2, r0, r1, r2, fill);
+                       m0, m1, m2, r0, r1, r2, fill, (Wo & 3) == 0 && ((uintptr_t)out & 15) == 0);
     return nkb_check_launch("image_prep");
 }

@@ -10,6 +10,10 @@ struct LossRow {
     float coef;   // d(row loss)/d(logit_j) = coef * (p_j - [j == y])   (before the 1/normaliser)
 };
 
+__device__ __forceinline__ bool argmax_takes(float v, int j, float mx, int am) {
+    return v > mx || (v != v && mx == mx) || ((v == mx || (v != v && mx != mx)) && j < am);
+}
+
 // kind: 0 = CrossEntropy(weight), 1 = Focal(alpha, gamma)
 __global__ void loss_fwd_kernel(const float* __restrict__ logits, int ld, const long long* __restrict__ target, int B,
                                 int C, int kind, const float* __restrict__ cls_w, float gamma, long long ignore_index,
@@ -20,17 +24,17 @@ __global__ void loss_fwd_kernel(const float* __restrict__ logits, int ld, const 
     const float* x = logits + (size_t)row * ld;
     float mx = -INFINITY;
     int am = 0x7fffffff;
+    // torch.argmax: the first maximum, a NaN above every number and the first NaN among several.  Equal candidates (equal values,
+    // or two NaNs) go to the smaller index, so a row of -inf ends at column 0 and a lane without a column (am = INT_MAX) never wins
     for (int j = lane; j < C; j += 64) {
         const float v = x[j];
-        if (v > mx || (v != v && mx == mx)) { mx = v; am = j; }   // first max wins; NaN wins like torch
+        if (argmax_takes(v, j, mx, am)) { mx = v; am = j; }
     }
-    // wave argmax (smallest index among equal maxima)
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         const float om = __shfl_xor(mx, o, 64);
         const int oa = __shfl_xor(am, o, 64);
-        const bool take = (om > mx) || (om != om && mx == mx) || (om == mx && oa < am);
-        if (take) { mx = om; am = oa; }
+        if (argmax_takes(om, oa, mx, am)) { mx = om; am = oa; }
     }
     float se = 0.f;
     for (int j = lane; j < C; j += 64) se += expf(x[j] - mx);
@@ -108,6 +112,10 @@ extern "C" int nkb_loss_forward(int kind, const float* logits, int ld, const lon
                                 const float* class_weight, float gamma, long long ignore_index, float* probs, int ldp,
                                 int* argmax, void* row_state, float* out2, int reduction, hipStream_t stream) {
     if ((unsigned)reduction > 2u) { nkb_set_error("loss_forward: reduction %d (0 mean, 1 sum, 2 none)", reduction); return 1; }
+    if ((unsigned)kind > 1u) { nkb_set_error("loss_forward: kind %d (0 cross entropy, 1 focal)", kind); return 1; }
+    if (B < 0 || C < 0) { nkb_set_error("loss_forward: negative extent (B %d, C %d)", B, C); return 1; }
+    if (row_state && !target) { nkb_set_error("loss_forward: row_state needs target"); return 1; }
+    if (B == 0 || C == 0) return 0;
     NkbProfScope prof(NKB_K_LOSS, stream, 0);
     hipLaunchKernelGGL(loss_fwd_kernel, dim3((B + 3) / 4), dim3(256), 0, stream, logits, ld, target, B, C, kind,
                        class_weight, gamma, ignore_index, probs, ldp, argmax, (LossRow*)row_state);
@@ -119,6 +127,8 @@ extern "C" size_t nkb_loss_row_state_bytes(int B) { return (size_t)B * sizeof(Lo
 extern "C" int nkb_loss_backward(const float* probs, int ldp, const long long* target, const void* row_state,
                                  const float* out2, const float* grad_out, int grad_out_per_row, int B, int C,
                                  float* dlogits, int ldd, hipStream_t stream) {
+    if (B < 0 || C < 0) { nkb_set_error("loss_backward: negative extent (B %d, C %d)", B, C); return 1; }
+    if (B == 0 || C == 0) return 0;
     NkbProfScope prof(NKB_K_LOSS, stream, 0);
     size_t g = ((size_t)B * C + 255) / 256;
     if (g > 2048) g = 2048;

@@ -179,17 +179,7 @@ extern "C" int nkb_optim_step(int kind, float* p, const float* g, float* m, floa
     return nkb_check_launch("optim_step");
 }
 
-// sum of squares of a flat fp32 range -> out[0] (+=, caller zeroes): per-parameter gradient norms (cfg.log_gradients)
-__global__ void sumsq_kernel(const float* __restrict__ x, size_t n, float* __restrict__ out) {
-    __shared__ float s[4];
-    float t = 0.f;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) t += x[i] * x[i];
-    t = wave_sum(t);
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = t;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, s[0] + s[1] + s[2] + s[3]);
-}
-// segments: offsets[k]..offsets[k+1] of one flat buffer -> out[k] = sum of squares
+// segments: offsets[k]..offsets[k+1] of one flat fp32 buffer -> out[k] = sum of squares: per-parameter gradient norms (cfg.log_gradients)
 __global__ void seg_sumsq_kernel(const float* __restrict__ x, const long long* __restrict__ offsets, int nseg,
                                  float* __restrict__ out) {
     const int k = blockIdx.x;
@@ -203,6 +193,8 @@ __global__ void seg_sumsq_kernel(const float* __restrict__ x, const long long* _
     if (threadIdx.x == 0) out[k] = s[0] + s[1] + s[2] + s[3];
 }
 extern "C" int nkb_segment_sumsq(const float* x, const long long* offsets, int nseg, float* out, hipStream_t stream) {
+    if (nseg < 0) { nkb_set_error("segment_sumsq: negative segment count %d", nseg); return 1; }
+    if (nseg == 0) return 0;
     NkbProfScope prof(NKB_K_MISC, stream, 0);
     hipLaunchKernelGGL(seg_sumsq_kernel, dim3(nseg), dim3(256), 0, stream, x, offsets, nseg, out);
     return nkb_check_launch("segment_sumsq");
