@@ -490,7 +490,32 @@ int nkb_wfold(int dtype, const float* w, const float* scale, void* dst, int Cout
  * flags [B] uint8 (bit 0 horizontal, bit 1 vertical flip; NULL = none), out [B][3][Ho][Wo] fp32 (device);
  * mean / stdev: 3 HOST floats each (fractions of 255 as in A.Normalize); fill: pad value in 0..255.
  * out[b][c][y][x] = (P - 255 mean[c]) * (1 / (255 stdev[c])), every operation in fp32.  out needs the alignment of a float only:
- * the 16-byte stores are taken where Wo % 4 == 0 and out is 16-byte aligned, element stores otherwise. */
+ * the 16-byte stores are taken where Wo % 4 == 0 and out is 16-byte aligned, element stores otherwise.
+ *
+ * Augmentation records (RandomBrightnessContrast -> HueSaturationValue -> CoarseDropout of the same stack, on the device).
+ * Flag bit 2 (value 4): image b has a record.  When ANY flag byte has bit 2, the flags buffer continues with a record table:
+ * it starts at byte offset roundup(B, 16), record b at table + 256 b, 64 little-endian 32-bit words each; the buffer is then
+ * 16-byte aligned and roundup(B, 16) + 256 B bytes long.  This function cannot see device bits: the layout is the caller's
+ * duty (hip.pack_image_aug keeps it).  The kernel reads record b only where flags[b] has bit 2.  Words (f = float32 bits):
+ *   0      apply mask: bit 0 brightness/contrast, bit 1 HSV shift, bit 2 holes
+ *   1 f, 2 f   alpha, offset (= float32 of beta * 255)            3 f, 4 f, 5 f   hue, saturation, value shift
+ *   6      number of holes, 0..12 (clamped)                       7..9   hole fill levels R, G, B        10..15  zero
+ *   16 + 4k .. 19 + 4k, k < 12   y1, x1, y2, x2 of hole k, half-open, in OUTPUT-canvas coordinates (after pad and flips)
+ * An image with a record goes through uint8 LEVELS, every fp32 step one operation (no contraction), on the padded and flipped
+ * canvas — pad pixels are augmented too:
+ *   1. P = source level, or the pad level clamp((int)fill, 0, 255);
+ *   2. brightness/contrast (albumentations' uint8 LUT, brightness_by_max): t = P; alpha != 1: t = t * alpha; offset != 0:
+ *      t = t + offset; level = trunc(clamp(t, 0, 255));
+ *   3. HSV shift, skipped when the three shifts are 0.  OpenCV's 8-bit conversions, restated (parity with cv2 is UNPINNED):
+ *      v = max, d = v - min, s = (d sdiv[v] + 2048) >> 12, hraw = g - b if v == r, else b - r + 2d if v == g, else r - g + 4d,
+ *      h = (hraw hdiv[d] + 2048) >> 12 (arithmetic), + 180 if negative; sdiv[v] = rint(255 * 4096 / v), hdiv[d] =
+ *      rint(180 * 4096 / (6 d)), both 0 at 0.  h = trunc(fmod(h + hue, 180) brought into [0, 180)), s = trunc(clamp(s + sat,
+ *      0, 255)), v likewise.  Back: hf = h * (6.f / 180.f), sf = s * (1.f / 255.f), vf = v * (1.f / 255.f); s == 0: all three vf;
+ *      else sector = floor(hf), f = hf - sector, tab = [vf, vf (1 - sf), vf (1 - sf f), vf (1 - sf (1 - f))], (b, g, r) =
+ *      tab[{{1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}}[sector]]; level = clamp(rint(x * 255), 0, 255), half to even;
+ *   4. holes: a pixel inside any of the first n boxes takes the fill levels;
+ *   5. Normalize as above on the level.
+ * Flag values 0..3 (and flags == NULL) give the bits they always gave. */
 int nkb_image_prep(const unsigned char* src, const int* sizes, const unsigned char* flags, float* out, int B, int Hs, int Ws,
                    int Ho, int Wo, const float* mean, const float* stdev, float fill, nkb_stream_t stream);
 /* out = keep ? in/(1-p) : 0 (+ add); forward draws keep from a hash of (seed, index) and stores it in mask */

@@ -10,14 +10,83 @@
 // HBM-bound: 3 B read + 12 B written per output pixel.  One thread = 4 consecutive x of one row, all three channels:
 // 12 source bytes (byte loads; neighbouring lanes cover neighbouring bytes) and three 16-byte stores, one per plane, where
 // Wo % 4 == 0 and `out` is 16-byte aligned (every row of every plane then is); element stores otherwise.
+//
+// Flag bit 2 marks an image with an augmentation record behind the flag bytes (include/nkbhip.h): its pixels go through
+// RandomBrightnessContrast -> HueSaturationValue -> CoarseDropout on uint8 levels between the load and the normalise step of
+// the same thread, so the colour augmentations of the stack cost no HBM traffic of their own.
 #include "common.h"
 
 namespace {
+
+// ---- augmentation records (flag bit 2; layout in include/nkbhip.h) ---------------------------------------------------------------
+// RandomBrightnessContrast -> HueSaturationValue -> CoarseDropout of the reference stack on uint8 LEVELS of the padded, flipped
+// canvas, every fp32 step its own operation (the build has -ffp-contract=off) so that tests/image_aug_reference.py reproduces
+// the levels in numpy float32.  The HSV conversions restate OpenCV's 8-bit ones: integer forward conversion with the two
+// 4096-scaled divisor tables, float inverse conversion.
+constexpr int kRecWords = 64, kMaxHoles = 12;
+
+// sdiv[v] = rint(255 * 4096 / v), hdiv[d] = rint(180 * 4096 / (6 d)), entry 0 = 0.  Neither quotient can end in .5 (that needs
+// 2^13 | v), so the integer round-half-up is rint.  Constant memory rather than LDS: the plain path then pays nothing for them —
+// no fill and no barrier in front of the first load; the 2 KB stay in the vector L1 for the lanes that index them.
+struct DivTable { int v[256]; };
+constexpr DivTable make_div_table(int num) {
+    DivTable t{};
+    for (int i = 1; i < 256; ++i) t.v[i] = (2 * num + i) / (2 * i);
+    return t;
+}
+__constant__ DivTable kSdiv = make_div_table(255 * 4096), kHdiv = make_div_table(30 * 4096);
+
+// albumentations' uint8 LUT: clip(level * alpha + beta * 255), truncated
+__device__ __forceinline__ int aug_brightness_contrast(int P, float alpha, float offset) {
+    float t = (float)P;
+    if (alpha != 1.f) t = t * alpha;
+    if (offset != 0.f) t = t + offset;
+    return (int)fminf(fmaxf(t, 0.f), 255.f);
+}
+
+__device__ __forceinline__ int aug_level(float x) { return (int)fminf(fmaxf(rintf(x * 255.f), 0.f), 255.f); }
+
+// r, g, b in 0..255 (so v and d index the 256-entry tables in range)
+__device__ __forceinline__ void aug_hsv(int& r, int& g, int& b, float hue, float sat, float val) {
+    const int v = max(r, max(g, b)), d = v - min(r, min(g, b));
+    int s = (d * kSdiv.v[v] + 2048) >> 12;
+    const int hraw = v == r ? g - b : v == g ? b - r + 2 * d : r - g + 4 * d;
+    int h = (hraw * kHdiv.v[d] + 2048) >> 12;
+    if (h < 0) h += 180;
+    float m = fmodf((float)h + hue, 180.f);
+    if (m < 0.f) m = m + 180.f;
+    h = (int)m;
+    if (h >= 180) h -= 180;
+    s = (int)fminf(fmaxf((float)s + sat, 0.f), 255.f);
+    const int v2 = (int)fminf(fmaxf((float)v + val, 0.f), 255.f);
+    const float hf = (float)h * (6.f / 180.f), sf = (float)s * (1.f / 255.f), vf = (float)v2 * (1.f / 255.f);
+    if (s == 0) {
+        r = g = b = aug_level(vf);
+        return;
+    }
+    const float fs = floorf(hf), f = hf - fs;
+    const int sector = min(max((int)fs, 0), 5);
+    const float t0 = vf, t1 = vf * (1.f - sf), t2 = vf * (1.f - sf * f), t3 = vf * (1.f - sf * (1.f - f));
+    float fb, fg, fr;        // (b, g, r) = tab[{{1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}}[sector]]
+    switch (sector) {
+        case 0: fb = t1; fg = t3; fr = t0; break;
+        case 1: fb = t1; fg = t0; fr = t2; break;
+        case 2: fb = t3; fg = t0; fr = t1; break;
+        case 3: fb = t0; fg = t2; fr = t1; break;
+        case 4: fb = t0; fg = t1; fr = t3; break;
+        default: fb = t2; fg = t1; fr = t0; break;
+    }
+    r = aug_level(fr);
+    g = aug_level(fg);
+    b = aug_level(fb);
+}
 
 __global__ __launch_bounds__(256) void image_prep_kernel(const unsigned char* __restrict__ src, const int* __restrict__ sizes,
                                                          const unsigned char* __restrict__ flags, float* __restrict__ out,
                                                          int B, int Hs, int Ws, int Ho, int Wo, float m0, float m1, float m2,
                                                          float r0, float r1, float r2, float fill, bool vec) {
+    const int* __restrict__ table = (const int*)(flags + (((size_t)B + 15) & ~(size_t)15));     // dereferenced only behind bit 2
+    const int padlv = (int)fminf(fmaxf(fill, 0.f), 255.f);
     const int xg = (Wo + 3) >> 2;                       // 4-pixel groups per row
     const long long total = (long long)B * Ho * xg;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -31,17 +100,63 @@ __global__ __launch_bounds__(256) void image_prep_kernel(const unsigned char* __
         const int sy = yf - top;
         const bool row_in = (unsigned)sy < (unsigned)h;
         const unsigned char* row = src + ((size_t)b * Hs + (row_in ? sy : 0)) * Ws * 3;
-        float v[3][4];
+        // the 12 source bytes are loaded and turned into the plain path's values in straight-line code, exactly as without records;
+        // lanes of an image with a record (per lane: a wave can straddle two images) then redo the arithmetic from the bytes
+        int q[3][4];
+        bool in[4];
+        float p[3][4];                                  // the value Normalize sees: a level, or `fill` itself on the plain path
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int x = gx * 4 + j;
             const int xf = (fl & 1u) ? Wo - 1 - x : x;
             const int sx = xf - left;
-            const bool in = row_in && (unsigned)sx < (unsigned)w && x < Wo;
-            const unsigned char* px = row + (in ? sx : 0) * 3;
-            v[0][j] = ((in ? (float)px[0] : fill) - m0) * r0;
-            v[1][j] = ((in ? (float)px[1] : fill) - m1) * r1;
-            v[2][j] = ((in ? (float)px[2] : fill) - m2) * r2;
+            in[j] = row_in && (unsigned)sx < (unsigned)w && x < Wo;
+            const unsigned char* px = row + (in[j] ? sx : 0) * 3;
+            q[0][j] = px[0]; q[1][j] = px[1]; q[2][j] = px[2];
+            p[0][j] = in[j] ? (float)q[0][j] : fill;
+            p[1][j] = in[j] ? (float)q[1][j] : fill;
+            p[2][j] = in[j] ? (float)q[2][j] : fill;
+        }
+        if (fl & 4u) {
+            const int* __restrict__ rec = table + (size_t)kRecWords * b;
+            const int mask = rec[0];
+            const float alpha = __int_as_float(rec[1]), offset = __int_as_float(rec[2]);
+            const float hue = __int_as_float(rec[3]), sat = __int_as_float(rec[4]), val = __int_as_float(rec[5]);
+            const bool bc = mask & 1, hsv = (mask & 2) && (hue != 0.f || sat != 0.f || val != 0.f);
+            int lv[3][4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                int cr = in[j] ? q[0][j] : padlv, cg = in[j] ? q[1][j] : padlv, cb = in[j] ? q[2][j] : padlv;
+                if (bc) {
+                    cr = aug_brightness_contrast(cr, alpha, offset);
+                    cg = aug_brightness_contrast(cg, alpha, offset);
+                    cb = aug_brightness_contrast(cb, alpha, offset);
+                }
+                if (hsv) aug_hsv(cr, cg, cb, hue, sat, val);
+                lv[0][j] = cr; lv[1][j] = cg; lv[2][j] = cb;
+            }
+            if (mask & 4) {                             // CoarseDropout: boxes in output-canvas coordinates, half-open
+                const int n = min(max(rec[6], 0), kMaxHoles);
+                const int f0 = rec[7], f1 = rec[8], f2 = rec[9];
+                for (int k = 0; k < n; ++k) {
+                    const int y1 = rec[16 + 4 * k], x1 = rec[17 + 4 * k], y2 = rec[18 + 4 * k], x2 = rec[19 + 4 * k];
+                    if (y < y1 || y >= y2) continue;
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const int x = gx * 4 + j;
+                        if (x >= x1 && x < x2) { lv[0][j] = f0; lv[1][j] = f1; lv[2][j] = f2; }
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { p[0][j] = (float)lv[0][j]; p[1][j] = (float)lv[1][j]; p[2][j] = (float)lv[2][j]; }
+        }
+        float v[3][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[0][j] = (p[0][j] - m0) * r0;
+            v[1][j] = (p[1][j] - m1) * r1;
+            v[2][j] = (p[2][j] - m2) * r2;
         }
         const size_t plane = (size_t)Ho * Wo;
         float* o = out + (size_t)b * 3 * plane + (size_t)y * Wo + gx * 4;

@@ -1,11 +1,16 @@
 """Minimal input side for train.py: `get_dataset(data, pipeline) -> DataLoader` (signature of
 /root/reference/nkb_classification/dataset.py:541-629).
 
-The reference's five annotation-file dataset types and the geometric / colour augmentations of its albumentations
-stack stay CPU-side input code outside the accelerated path and are not rebuilt.  What IS here:
+The reference's five annotation-file dataset types stay CPU-side input code outside the accelerated path and are not
+rebuilt, and of its albumentations stack only what its two training configs use is.  What IS here:
   * `DeviceLoader`: the loader hands over pinned **uint8** HWC batches; the H2D copy runs on a copy stream one batch
-    ahead of the train step, and the pad -> flip -> normalise -> CHW tail of the pipeline (configs/singletask_config.py:
-    162-219) runs on the GPU (`nkb_image_prep`), so engine.py:40's `img.to(device)` finds the batch already resident;
+    ahead of the train step, and everything behind LongestMaxSize in the stack of configs/singletask_config.py:162-201 —
+    PadIfNeeded -> HorizontalFlip -> VerticalFlip -> RandomBrightnessContrast -> HueSaturationValue -> CoarseDropout ->
+    Normalize -> ToTensorV2 — runs on the GPU in one launch (`nkb_image_prep`), so engine.py:40's `img.to(device)` finds
+    the batch already resident.  The three augmentations are per-image records drawn here (`draw_image_aug`, from a
+    second generator seeded `seed + 1`) and carried behind the flag bytes (`hip.pack_image_aug`); `translate_pipeline`
+    reads them off an albumentations-style Compose.  Sampling rules and attribute names restate albumentations 1.x, the
+    kernel's 8-bit HSV conversions restate OpenCV's — from memory, neither is a dependency: parity with them is UNPINNED;
   * `ImbalancedDatasetSampler` (dataset.py:27-86: weights 1 / count[label], `torch.multinomial` with replacement) and
     `ShardedSampler` (one process per GPU: rank r takes indices r::W of a seed-shared permutation);
   * `get_dataset` honours `shuffle`, `weighted_sampling`, `drop_last`, `num_workers` (dataset.py:606-628).
@@ -136,25 +141,241 @@ class ShardedSampler(Sampler):
         return self.num_samples
 
 
+# ---- device-side colour augmentations and CoarseDropout: the host draws -------------------------------------------------------------
+# The kernel applies what a per-image record says (include/nkbhip.h); this is where the records come from.  Argument names
+# and sampling rules restate albumentations 1.x from memory (the library is not a dependency): parity with it is UNPINNED.
+AUG_KEYS = ("brightness_contrast", "hue_saturation_value", "coarse_dropout")
+MAX_HOLES = 12
+_AUG_DEFAULTS = {
+    "brightness_contrast": dict(brightness_limit=0.2, contrast_limit=0.2, brightness_by_max=True, p=0.5),
+    "hue_saturation_value": dict(hue_shift_limit=20, sat_shift_limit=30, val_shift_limit=20, p=0.5),
+    "coarse_dropout": dict(max_holes=8, max_height=8, max_width=8, min_holes=None, min_height=None, min_width=None,
+                           fill_value=0, p=0.5),
+}
+
+
+def _limit(x):
+    """a scalar limit x means (-x, x); a pair is kept in its order (random.uniform takes reversed bounds as they are)"""
+    if isinstance(x, (tuple, list)):
+        if len(x) != 2:
+            raise ValueError(f"a limit is a number or a pair, got {x!r}")
+        return (x[0], x[1])
+    return (-x, x)
+
+
+def normalise_aug_spec(spec):
+    """{key of AUG_KEYS: None or dict of albumentations' argument names plus p} -> the same with defaults filled in, limits as
+    pairs and the fill value as three uint8 levels; None when no transform is asked for.  Refuses what the kernel cannot do."""
+    spec = spec or {}
+    unknown = set(spec) - set(AUG_KEYS)
+    if unknown:
+        raise ValueError(f"unknown augmentation keys {sorted(unknown)}; known: {AUG_KEYS}")
+    out = {}
+    for key in AUG_KEYS:
+        if spec.get(key) is None:
+            continue
+        extra = set(spec[key]) - set(_AUG_DEFAULTS[key])
+        if extra:
+            raise ValueError(f"{key}: unknown arguments {sorted(extra)}; known: {sorted(_AUG_DEFAULTS[key])}")
+        out[key] = {**_AUG_DEFAULTS[key], **spec[key]}
+    if not out:
+        return None
+    bc, hsv, cd = (out.get(k) for k in AUG_KEYS)
+    if bc is not None:
+        if not bc["brightness_by_max"]:
+            raise NotImplementedError("brightness_contrast: only brightness_by_max=True (offset = beta * 255) is built")
+        bc["brightness_limit"], bc["contrast_limit"] = _limit(bc["brightness_limit"]), _limit(bc["contrast_limit"])
+    if hsv is not None:
+        for k in ("hue_shift_limit", "sat_shift_limit", "val_shift_limit"):
+            hsv[k] = _limit(hsv[k])
+    if cd is not None:
+        for k in ("holes", "height", "width"):
+            if cd["min_" + k] is None:
+                cd["min_" + k] = cd["max_" + k]
+        if cd["max_holes"] > MAX_HOLES:
+            raise ValueError(f"coarse_dropout: max_holes = {cd['max_holes']} exceeds the {MAX_HOLES} boxes a record holds")
+        if not 0 <= cd["min_holes"] <= cd["max_holes"]:
+            raise ValueError(f"coarse_dropout: need 0 <= min_holes <= max_holes, got {cd['min_holes']}, {cd['max_holes']}")
+        for k in ("height", "width"):
+            lo, hi = cd["min_" + k], cd["max_" + k]
+            if isinstance(lo, float) != isinstance(hi, float) or not 0 <= lo <= hi or (isinstance(hi, float) and hi >= 1.0):
+                raise ValueError(f"coarse_dropout: min_{k} / max_{k} are both pixel counts or both fractions below 1 with "
+                                 f"min <= max, got {lo!r}, {hi!r}")
+        fv = cd["fill_value"]
+        if isinstance(fv, str):
+            raise NotImplementedError(f"coarse_dropout: fill_value {fv!r} is not built (numbers only)")
+        fv = np.broadcast_to(np.asarray(fv, np.float64), (3,))
+        cd["fill_value"] = tuple(int(a) for a in fv.astype(np.int64).astype(np.uint8))    # as numpy casts into a uint8 image
+    return out
+
+
+def aug_table_columns(spec):
+    """K of the per-batch torch.rand(B, K) table (spec: normalised)"""
+    k = 0
+    if "brightness_contrast" in spec:
+        k += 3
+    if "hue_saturation_value" in spec:
+        k += 4
+    if "coarse_dropout" in spec:
+        k += 2 + 4 * spec["coarse_dropout"]["max_holes"]
+    return k
+
+
+def _uniform(lim, u):
+    return lim[0] + (lim[1] - lim[0]) * u
+
+
+def _randint(lo, hi, u):
+    """random.randint(lo, hi) (both ends included) from a uniform u in [0, 1)"""
+    return np.minimum(lo + np.floor(u * (hi - lo + 1)).astype(np.int64), hi)
+
+
+def draw_image_aug(gen, B, size, spec):
+    """The augmentation draws of one batch -> (bits uint8 [B]: 4 where the image has a record, records int32 [B, 64]).
+
+    ONE table u = torch.rand(B, K, generator=gen) per batch, K = aug_table_columns(spec), columns in this fixed order (a
+    transform that is None takes no columns; every column is drawn whether or not its transform applies to the image):
+      brightness_contrast   [apply, contrast, brightness]: applied where apply < p; alpha = 1 + U(contrast_limit),
+                            beta = U(brightness_limit), offset = float32(beta * 255);
+      hue_saturation_value  [apply, hue, sat, val]: float shifts U(limit);
+      coarse_dropout        [apply, count, then (height, width, y, x) for each of max_holes boxes]: n = randint(min_holes,
+                            max_holes) boxes, the first n quadruples; hole height int(size * U(min, max)) for fractions,
+                            randint(min, max) for pixel counts (width alike); y1 = randint(0, size - height), x1 alike.
+    U(lo, hi) = lo + (hi - lo) u and randint(lo, hi) = lo + floor(u (hi - lo + 1)), as random.uniform / random.randint."""
+    from .hip import IMAGE_AUG_BIT, IMAGE_AUG_WORDS
+    spec = normalise_aug_spec(spec)
+    rec = np.zeros((B, IMAGE_AUG_WORDS), np.int32)
+    if spec is None:
+        return torch.zeros(B, dtype=torch.uint8), torch.from_numpy(rec)
+    u = torch.rand(B, aug_table_columns(spec), generator=gen).double().numpy()
+    f = rec.view(np.float32)
+    f[:, 1] = 1.0
+    col = 0
+    bc, hsv, cd = (spec.get(k) for k in AUG_KEYS)
+    if bc is not None:
+        on = u[:, col] < bc["p"]
+        alpha = 1.0 + _uniform(bc["contrast_limit"], u[:, col + 1])
+        beta = _uniform(bc["brightness_limit"], u[:, col + 2])
+        rec[:, 0] |= on.astype(np.int32)
+        f[:, 1] = np.where(on, alpha, 1.0).astype(np.float32)
+        f[:, 2] = np.where(on, beta * 255.0, 0.0).astype(np.float32)
+        col += 3
+    if hsv is not None:
+        on = u[:, col] < hsv["p"]
+        rec[:, 0] |= on.astype(np.int32) << 1
+        for j, k in enumerate(("hue_shift_limit", "sat_shift_limit", "val_shift_limit")):
+            f[:, 3 + j] = np.where(on, _uniform(hsv[k], u[:, col + 1 + j]), 0.0).astype(np.float32)
+        col += 4
+    if cd is not None:
+        on = u[:, col] < cd["p"]
+        rec[:, 0] |= on.astype(np.int32) << 2
+        n = _randint(cd["min_holes"], cd["max_holes"], u[:, col + 1])
+        rec[:, 6] = np.where(on, n, 0)
+        rec[:, 7:10] = np.where(on[:, None], np.asarray(cd["fill_value"], np.int32), 0)
+        col += 2
+        for k in range(cd["max_holes"]):
+            ext = []
+            for j, name in enumerate(("height", "width")):
+                lo, hi = cd["min_" + name], cd["max_" + name]
+                if isinstance(hi, float):
+                    ext.append((size * _uniform((lo, hi), u[:, col + j])).astype(np.int64))
+                else:
+                    ext.append(np.minimum(_randint(lo, hi, u[:, col + j]), size))
+            y1 = _randint(0, size - ext[0], u[:, col + 2])
+            x1 = _randint(0, size - ext[1], u[:, col + 3])
+            box = np.stack([y1, x1, y1 + ext[0], x1 + ext[1]], 1)
+            rec[:, 16 + 4 * k:20 + 4 * k] = np.where((on & (k < n))[:, None], box, 0)
+            col += 4
+    bits = np.where(rec[:, 0] != 0, IMAGE_AUG_BIT, 0).astype(np.uint8)
+    return torch.from_numpy(bits), torch.from_numpy(rec)
+
+
+# transforms of the reference stack, in the only order the kernel applies them
+_PIPELINE_ORDER = ("LongestMaxSize", "PadIfNeeded", "HorizontalFlip", "VerticalFlip", "RandomBrightnessContrast",
+                   "HueSaturationValue", "CoarseDropout", "Normalize", "ToTensorV2")
+
+
+def translate_pipeline(pipeline):
+    """An albumentations-style Compose (anything with a `.transforms` list) -> the `data` keys of the device pipeline.
+    Duck-typed on type(t).__name__ and on the attributes p, max_size, value, brightness_limit, contrast_limit,
+    hue_shift_limit, sat_shift_limit, val_shift_limit, min/max_holes, min/max_height, min/max_width, fill_value, mean, std
+    (restated from memory of albumentations 1.x: UNPINNED).  A transform outside the reference stack, or one out of the
+    stack's order, raises NotImplementedError."""
+    out, last = {}, -1
+    for t in pipeline.transforms:
+        name = type(t).__name__
+        if name not in _PIPELINE_ORDER:
+            raise NotImplementedError(f"device pipeline: transform {name} is not built (known: {', '.join(_PIPELINE_ORDER)})")
+        rank = _PIPELINE_ORDER.index(name)
+        if rank <= last:
+            raise NotImplementedError(f"device pipeline: {name} after {_PIPELINE_ORDER[last]} — the kernel applies the stack "
+                                      f"in the order {' -> '.join(_PIPELINE_ORDER)} only")
+        last = rank
+        p = float(getattr(t, "p", 1.0))
+        if name == "LongestMaxSize":
+            if getattr(t, "max_size", None) is not None:
+                out["size"] = int(t.max_size)
+        elif name == "PadIfNeeded":
+            if getattr(t, "value", None) is not None:
+                out["fill"] = float(t.value)
+        elif name == "HorizontalFlip":
+            out["hflip_p"] = p
+        elif name == "VerticalFlip":
+            out["vflip_p"] = p
+        elif name == "RandomBrightnessContrast":
+            out["brightness_contrast"] = dict(brightness_limit=t.brightness_limit, contrast_limit=t.contrast_limit, p=p,
+                                              brightness_by_max=getattr(t, "brightness_by_max", True))
+        elif name == "HueSaturationValue":
+            out["hue_saturation_value"] = dict(hue_shift_limit=t.hue_shift_limit, sat_shift_limit=t.sat_shift_limit,
+                                               val_shift_limit=t.val_shift_limit, p=p)
+        elif name == "CoarseDropout":
+            out["coarse_dropout"] = dict(p=p, **{k: getattr(t, k) for k in ("max_holes", "min_holes", "max_height", "min_height",
+                                                                          "max_width", "min_width", "fill_value") if hasattr(t, k)})
+        elif name == "Normalize":
+            out["mean"], out["std"] = tuple(t.mean), tuple(t.std)
+    return out
+
+
 class DeviceLoader:
     """Wraps a host loader that yields (uint8 [B,H,W,3], sizes int32 [B,2] or None, target) and yields
     (float32 [B,3,size,size] on `device`, target) — the batch format engine.train_epoch consumes (engine.py:39-41).
 
     Batch k+1 is pinned and copied on a dedicated copy stream while batch k trains; the prep kernel runs on the compute
     stream after an event wait, so no host synchronisation is added.  Flip draws come from a host generator (one
-    Bernoulli per image and axis, A.HorizontalFlip / A.VerticalFlip(p))."""
+    Bernoulli per image and axis, A.HorizontalFlip / A.VerticalFlip(p)).
+
+    brightness_contrast / hue_saturation_value / coarse_dropout: None or a dict of albumentations' argument names plus `p`
+    (normalise_aug_spec).  Their draws (draw_image_aug) come from a SECOND generator seeded `seed + 1`, never from the flip
+    generator; the records ride behind the flag bytes (hip.pack_image_aug) on the copy stream.  With all three None nothing
+    changes: same draws, same buffers."""
 
     def __init__(self, loader, device, size, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), hflip_p=0.0,
-                 vflip_p=0.0, fill=0.0, seed=0):
+                 vflip_p=0.0, fill=0.0, seed=0, brightness_contrast=None, hue_saturation_value=None, coarse_dropout=None):
         self.loader, self.device = loader, torch.device(device)
         self.size, self.mean, self.std, self.fill = size, tuple(mean), tuple(std), float(fill)
         self.hflip_p, self.vflip_p = float(hflip_p), float(vflip_p)
         self.gen = torch.Generator().manual_seed(seed)
+        self.aug = normalise_aug_spec(dict(brightness_contrast=brightness_contrast, hue_saturation_value=hue_saturation_value,
+                                           coarse_dropout=coarse_dropout))
+        self.aug_gen = torch.Generator().manual_seed(seed + 1)
         self.dataset = getattr(loader, "dataset", None)
         self._copy = None
 
     def __len__(self):
         return len(self.loader)
+
+    def draw_flags(self, B):
+        """The host draws of one batch -> what nkb_image_prep takes as `flags`: None, uint8 [B] flip bits (one torch.rand(B, 2)
+        from the flip generator), or, with augmentations on, those bits | the record bits with the record table behind them."""
+        flags = None
+        if self.hflip_p > 0 or self.vflip_p > 0:
+            u = torch.rand(B, 2, generator=self.gen)
+            flags = ((u[:, 0] < self.hflip_p).to(torch.uint8) | ((u[:, 1] < self.vflip_p).to(torch.uint8) << 1))
+        if self.aug is not None:
+            from . import hip
+            bits, records = draw_image_aug(self.aug_gen, B, self.size, self.aug)
+            flags = hip.pack_image_aug(bits if flags is None else flags | bits, records)
+        return flags
 
     def _stage(self, item):
         """Pinned host batch -> device uint8 on the copy stream; returns what the compute stream needs."""
@@ -164,11 +385,7 @@ class DeviceLoader:
             (raw, target), sizes = item, None
         if raw.dtype != torch.uint8 or raw.dim() != 4 or raw.shape[-1] != 3:
             raise RuntimeError(f"DeviceLoader expects uint8 [B,H,W,3] batches, got {tuple(raw.shape)} {raw.dtype}")
-        B = raw.shape[0]
-        flags = None
-        if self.hflip_p > 0 or self.vflip_p > 0:
-            u = torch.rand(B, 2, generator=self.gen)
-            flags = ((u[:, 0] < self.hflip_p).to(torch.uint8) | ((u[:, 1] < self.vflip_p).to(torch.uint8) << 1))
+        flags = self.draw_flags(raw.shape[0])
         if self._copy is None:
             self._copy = torch.cuda.Stream(device=self.device)
         pin = lambda t: t if t is None or t.is_pinned() else t.contiguous().pin_memory()       # noqa: E731
@@ -221,10 +438,14 @@ class DeviceLoader:
 def get_dataset(data, pipeline=None):
     """dataset.py:541-629.  Extra keys: `device_pipeline=True` (+ `device`, `hflip_p`, `vflip_p`, `mean`, `std`) wraps the
     folder loader in a DeviceLoader; `rank` / `world` (+ `shard_seed`, the seed of the permutation all ranks share) shard the data for one-process-per-GPU
-    training."""
+    training.  With `device_pipeline` the keys `brightness_contrast`, `hue_saturation_value`, `coarse_dropout` (None or a dict of
+    albumentations' argument names plus `p`) and `fill` go to the DeviceLoader too, and a `pipeline` that has a `.transforms`
+    list is translated into all of these keys (translate_pipeline); explicit `data` keys win over the translated ones."""
     kind = data.get("type", "folder")
-    size = data.get("size", 224)
     on_device = bool(data.get("device_pipeline", False))
+    if on_device and isinstance(getattr(pipeline, "transforms", None), (list, tuple)):
+        data = {**translate_pipeline(pipeline), **data}
+    size = data.get("size", 224)
     if kind == "synthetic":
         ds = SyntheticDataset(data["n_images"], data["classes"], size=size, seed=data.get("seed", 1234))
         on_device = False
@@ -247,5 +468,6 @@ def get_dataset(data, pipeline=None):
     if on_device:
         return DeviceLoader(loader, data.get("device", "cuda:0"), size, mean=data.get("mean", (0.485, 0.456, 0.406)),
                             std=data.get("std", (0.229, 0.224, 0.225)), hflip_p=data.get("hflip_p", 0.0),
-                            vflip_p=data.get("vflip_p", 0.0), seed=data.get("seed", 0))
+                            vflip_p=data.get("vflip_p", 0.0), fill=data.get("fill", 0.0), seed=data.get("seed", 0),
+                            **{k: data.get(k) for k in AUG_KEYS})
     return loader

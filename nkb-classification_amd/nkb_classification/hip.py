@@ -935,7 +935,36 @@ def wfold(dtype, w, scale, dst, Cout, K):
     check(load().nkb_wfold(dtype, ptr(w), ptr(scale), ptr(dst), Cout, K, stream()), "wfold")
 
 
+IMAGE_AUG_BIT, IMAGE_AUG_WORDS, IMAGE_AUG_MAX_HOLES = 4, 64, 12     # flag bit 2, words per record, boxes per record (nkbhip.h)
+
+
+def image_aug_bytes(B):
+    """length of a flags buffer that carries records: the B flag bytes rounded up to 16, then 256 bytes per image"""
+    return (B + 15) // 16 * 16 + 4 * IMAGE_AUG_WORDS * B
+
+
+def pack_image_aug(flags, records):
+    """flags uint8 [B] (bit 0 / 1 flips, bit 2 = IMAGE_AUG_BIT: this image has a record), records int32 [B, 64] (host tensors)
+    -> the uint8 buffer nkb_image_prep reads when a bit 2 is set: flags, zero pad to 16 bytes, the record table.  Pinned when
+    both inputs are pinned.  The kernel reads record b only where flags[b] has bit 2, whatever the other records hold."""
+    B = flags.numel()
+    if flags.dtype != torch.uint8 or records.dtype != torch.int32 or tuple(records.shape) != (B, IMAGE_AUG_WORDS):
+        raise RuntimeError(f"pack_image_aug: expected uint8 [B] flags and int32 [B, {IMAGE_AUG_WORDS}] records, got "
+                           f"{tuple(flags.shape)} {flags.dtype} and {tuple(records.shape)} {records.dtype}")
+    if flags.is_cuda or records.is_cuda:
+        raise RuntimeError("pack_image_aug: packs host tensors (the buffer then crosses with the batch)")
+    off = (B + 15) // 16 * 16
+    buf = torch.zeros(image_aug_bytes(B), dtype=torch.uint8, pin_memory=flags.is_pinned() and records.is_pinned())
+    buf[:B] = flags.reshape(-1)
+    buf[off:] = records.contiguous().view(torch.uint8).reshape(-1)
+    return buf
+
+
 def image_prep(src, sizes, flags, out, B, Hs, Ws, Ho, Wo, mean, std, fill=0.0):
+    """flags: None, uint8 [B], or the buffer of pack_image_aug (the C side cannot see device bits: the layout is kept here)"""
+    if flags is not None and flags.numel() > B and (flags.numel() != image_aug_bytes(B) or flags.data_ptr() % 16):
+        raise RuntimeError(f"image_prep: a flags buffer longer than B = {B} must be the 16-byte aligned {image_aug_bytes(B)}-byte "
+                           f"layout of pack_image_aug, got {flags.numel()} bytes at offset {flags.data_ptr() % 16}")
     m, sd = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
     check(load().nkb_image_prep(ptr(src), ptr(sizes), ptr(flags), ptr(out), B, Hs, Ws, Ho, Wo, C.cast(m, C.c_void_p),
                                 C.cast(sd, C.c_void_p), float(fill), stream()), "image_prep")
