@@ -499,7 +499,7 @@ int nkb_wfold(int dtype, const float* w, const float* scale, void* dst, int Cout
  * duty (hip.pack_image_aug keeps it).  The kernel reads record b only where flags[b] has bit 2.  Words (f = float32 bits):
  *   0      apply mask: bit 0 brightness/contrast, bit 1 HSV shift, bit 2 holes
  *   1 f, 2 f   alpha, offset (= float32 of beta * 255)            3 f, 4 f, 5 f   hue, saturation, value shift
- *   6      number of holes, 0..12 (clamped)                       7..9   hole fill levels R, G, B        10..15  zero
+ *   6      number of holes, 0..12 (clamped)                       7..9   hole fill levels R, G, B        10..15  mixing (below)
  *   16 + 4k .. 19 + 4k, k < 12   y1, x1, y2, x2 of hole k, half-open, in OUTPUT-canvas coordinates (after pad and flips)
  * An image with a record goes through uint8 LEVELS, every fp32 step one operation (no contraction), on the padded and flipped
  * canvas — pad pixels are augmented too:
@@ -515,7 +515,21 @@ int nkb_wfold(int dtype, const float* w, const float* scale, void* dst, int Cout
  *      tab[{{1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}}[sector]]; level = clamp(rint(x * 255), 0, 255), half to even;
  *   4. holes: a pixel inside any of the first n boxes takes the fill levels;
  *   5. Normalize as above on the level.
- * Flag values 0..3 (and flags == NULL) give the bits they always gave. */
+ * Flag values 0..3 (and flags == NULL) give the bits they always gave.
+ *
+ * Mixing (Mixup / CutMix inside the same launch).  Flag bit 3 (value 8): image b is mixed with a partner image of the batch.  The
+ * record table is present when ANY flag byte has bit 2 or bit 3.  The kernel reads words 10..15 of record b only where flags[b] has
+ * bit 3, and words 0..9 and 16.. of record k only where flags[k] has bit 2 (k = b, or a partner).  Words of record b:
+ *   10     partner image index p in [0, B)                        11   1 = blend (Mixup), 2 = box (CutMix)
+ *   blend: 12 f, 13 f   lam, oml (the host stores oml = float32(1) - lam)      14, 15   zero
+ *   box:   12..15       y1, x1, y2, x2, half-open, in OUTPUT-canvas coordinates
+ * Let plain(k)[c][y][x] be the value this function writes for image k at that position when no image is mixed: it uses k's own
+ * sizes, pad, flips (bits 0, 1 of flags[k]) and augmentation record (bit 2).  Bit 3 of the PARTNER is ignored: no chaining.
+ *   blend: out[b] = lam * plain(b) + oml * plain(p): two fp32 multiplies, then one add, no contraction;
+ *   box:   out[b] = plain(p) inside the box, plain(b) outside.
+ * p == b is a no-op (out[b] = plain(b), also for a blend); so is a partner outside [0, B) or a mode other than 1 or 2, which
+ * hip.pack_image_aug refuses on the host.  The kernel reads only src through a partner.  Flag values 0..7 give the bits they gave
+ * before bit 3 existed. */
 int nkb_image_prep(const unsigned char* src, const int* sizes, const unsigned char* flags, float* out, int B, int Hs, int Ws,
                    int Ho, int Wo, const float* mean, const float* stdev, float fill, nkb_stream_t stream);
 /* out = keep ? in/(1-p) : 0 (+ add); forward draws keep from a hash of (seed, index) and stores it in mask */
@@ -524,6 +538,7 @@ int nkb_dropout(int dtype, int backward, const void* in, const void* add, void* 
 int nkb_colsum2d(int dtype, const void* x, float* out, long long rows, int C, long long ld, float* workspace,
                  nkb_stream_t stream);   /* workspace: NULL (atomics) or >= 256 * C floats (ordered two-stage sum) */
 
+#define NKB_LOSS_MIXED 16 /* nkb_loss_forward: kind | NKB_LOSS_MIXED = two labels and a weight per row (Mixup / CutMix), smoothing */
 /* Losses (kind 0: CrossEntropyLoss(weight); kind 1: FocalLoss(alpha, gamma) over un-ignored rows, losses.py:59-94).
  * reduction 0 "mean": out2[0] = loss, out2[1] = 1/normaliser; 1 "sum" / 2 "none": out2[0] = sum, out2[1] = 1 (the per-row
  * losses of "none" are row_state[i].loss, three floats per row).  A label outside [0, C) that is not ignore_index makes the
@@ -532,7 +547,33 @@ int nkb_colsum2d(int dtype, const void* x, float* out, long long rows, int C, lo
  * probs/argmax double as the logger's softmax/argmax (target, row_state and out2 NULL); argmax equals torch.argmax on every row:
  * the first maximum, a NaN above every number, the first NaN among several, column 0 for a row of -inf.  Any other kind, a
  * reduction outside 0..2, row_state without target and negative B or C are refused; B == 0 or C == 0 returns 0 without a launch
- * (backward as well) and writes nothing. */
+ * (backward as well) and writes nothing.
+ *
+ * Mixed form: kind NKB_LOSS_MIXED | 0 (cross entropy) or NKB_LOSS_MIXED | 1 (focal); every other kind stays refused.
+ *   target     int64 [3][B]: row 0 = y, row 1 = y2, row 2 = the float64 bit pattern of lam_b (rounded to fp32 by the kernel;
+ *              oml = 1.f - lam).  lam lives in device memory only.
+ *   gamma      cross entropy: the label-smoothing eps in [0, 1) (anything else is refused); focal: gamma (no smoothing).
+ *   row_state  32 B + 4 C bytes (nkb_loss_row_state_bytes is for kinds 0 and 1 only): B records of eight 32-bit words
+ *              {f loss, f wsum, f A, f c1, f c2, i sm, 0, 0}, then C floats ew[j] = (eps / C) * w_j (w = 1 without class weights;
+ *              all 0 for focal; eps / C is one fp32 division on the host).  sm = 1 where the row takes the smoothing term.
+ *   A row is dropped (record all zero) when EITHER label equals ignore_index; either label outside [0, C) and not ignored gives
+ *   loss NaN, wsum 1, A = c1 = c2 = NaN.  An all-dropped batch gives loss 0 and factor 0.  Reductions, out2, probs and argmax are
+ *   those of kinds 0 and 1; the per-row losses of "none" are the first float of each 32-byte record.
+ *   Operation order (fp32, one rounding per operation, lp_c = x_c - lse with lse = max + logf(sum), w1 = w[y], w2 = w[y2]):
+ *     cross entropy  c1 = (lam * (1.f - eps)) * w1;  c2 = (oml * (1.f - eps)) * w2;  hard = c1 * lp_y + c2 * lp_y2;
+ *                    eps > 0: S = sum_j ew_j * lp_j, SW = sum_j ew_j (each lane of the row's wave adds its columns j = lane,
+ *                    lane + 64, .. in rising order, then the wave's xor butterfly), loss = -(hard + S), A = (c1 + c2) + SW, sm = 1;
+ *                    eps == 0: loss = -hard, A = c1 + c2, sm = 0 (no term of a column other than y and y2 is formed);
+ *                    wsum = lam * w1 + oml * w2.  "mean" divides by sum wsum: at lam = 1, y2 = y this is
+ *                    F.cross_entropy(weight, label_smoothing); unweighted it is soft-target cross entropy over B.
+ *     focal          per label L_i = ((-w_i) * f_i) * lp_i, k_i = w_i * (f_i - (fm1_i * pt_i) * lp_i) exactly as kind 1 (its
+ *                    pt -> 1 guard included); loss = lam * L_1 + oml * L_2, c1 = lam * k_1, c2 = oml * k_2, A = c1 + c2, wsum = 1.
+ *   A coefficient that is 0 still multiplies its log p: lam = 1 with p_y2 == 0 gives 0 * -inf = NaN, as torch's
+ *   probability targets do.
+ * nkb_loss_backward: grad_out_per_row is a bit field.  Bit 0: one grad_out per row (else one scalar).  Bit 1 (value 2): row_state
+ * holds the records of a mixed forward and target is its [3][B] table; then, with g = grad_out[r or 0] * out2[1],
+ *     t = A_r * p_rj;  j == y_r: t = t - c1_r;  j == y2_r: t = t - c2_r;  sm_r: t = t - ew_j;  dlogits[r][j] = g * t
+ * (y2 == y: both differences land on the one column, c1 first).  Values above 3 are refused. */
 int nkb_loss_forward(int kind, const float* logits, int ld, const long long* target, int B, int C,
                      const float* class_weight, float gamma, long long ignore_index, float* probs, int ldp,
                      int* argmax, void* row_state, float* out2, int reduction, nkb_stream_t stream);

@@ -81,82 +81,133 @@ __device__ __forceinline__ void aug_hsv(int& r, int& g, int& b, float hue, float
     b = aug_level(fb);
 }
 
+// One 4-pixel group of image k at output row y, groups gx: source bytes -> the value the un-mixed kernel writes there (plain(k) of
+// include/nkbhip.h), from k's own sizes, pad, flips (fl bits 0, 1) and augmentation record (fl bit 2).  Bit 3 of fl is not looked at.
+__device__ __forceinline__ void prep_group(const unsigned char* __restrict__ src, const int* __restrict__ sizes,
+                                           const int* __restrict__ table, int k, unsigned fl, int y, int gx, int Hs, int Ws, int Ho,
+                                           int Wo, float m0, float m1, float m2, float r0, float r1, float r2, float fill,
+                                           float (&v)[3][4]) {
+    const int h = sizes ? sizes[2 * k] : Hs, w = sizes ? sizes[2 * k + 1] : Ws;
+    const int top = (Ho - h) / 2, left = (Wo - w) / 2;
+    const int yf = (fl & 2u) ? Ho - 1 - y : y;
+    const int sy = yf - top;
+    const bool row_in = (unsigned)sy < (unsigned)h;
+    const unsigned char* row = src + ((size_t)k * Hs + (row_in ? sy : 0)) * Ws * 3;
+    // the 12 source bytes are loaded and turned into the plain path's values in straight-line code, exactly as without records;
+    // lanes of an image with a record (per lane: a wave can straddle two images) then redo the arithmetic from the bytes
+    int q[3][4];
+    bool in[4];
+    float p[3][4];                                  // the value Normalize sees: a level, or `fill` itself on the plain path
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int x = gx * 4 + j;
+        const int xf = (fl & 1u) ? Wo - 1 - x : x;
+        const int sx = xf - left;
+        in[j] = row_in && (unsigned)sx < (unsigned)w && x < Wo;
+        const unsigned char* px = row + (in[j] ? sx : 0) * 3;
+        q[0][j] = px[0]; q[1][j] = px[1]; q[2][j] = px[2];
+        p[0][j] = in[j] ? (float)q[0][j] : fill;
+        p[1][j] = in[j] ? (float)q[1][j] : fill;
+        p[2][j] = in[j] ? (float)q[2][j] : fill;
+    }
+    if (fl & 4u) {
+        const int padlv = (int)fminf(fmaxf(fill, 0.f), 255.f);
+        const int* __restrict__ rec = table + (size_t)kRecWords * k;
+        const int mask = rec[0];
+        const float alpha = __int_as_float(rec[1]), offset = __int_as_float(rec[2]);
+        const float hue = __int_as_float(rec[3]), sat = __int_as_float(rec[4]), val = __int_as_float(rec[5]);
+        const bool bc = mask & 1, hsv = (mask & 2) && (hue != 0.f || sat != 0.f || val != 0.f);
+        int lv[3][4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int cr = in[j] ? q[0][j] : padlv, cg = in[j] ? q[1][j] : padlv, cb = in[j] ? q[2][j] : padlv;
+            if (bc) {
+                cr = aug_brightness_contrast(cr, alpha, offset);
+                cg = aug_brightness_contrast(cg, alpha, offset);
+                cb = aug_brightness_contrast(cb, alpha, offset);
+            }
+            if (hsv) aug_hsv(cr, cg, cb, hue, sat, val);
+            lv[0][j] = cr; lv[1][j] = cg; lv[2][j] = cb;
+        }
+        if (mask & 4) {                             // CoarseDropout: boxes in output-canvas coordinates, half-open
+            const int n = min(max(rec[6], 0), kMaxHoles);
+            const int f0 = rec[7], f1 = rec[8], f2 = rec[9];
+            for (int t = 0; t < n; ++t) {
+                const int y1 = rec[16 + 4 * t], x1 = rec[17 + 4 * t], y2 = rec[18 + 4 * t], x2 = rec[19 + 4 * t];
+                if (y < y1 || y >= y2) continue;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int x = gx * 4 + j;
+                    if (x >= x1 && x < x2) { lv[0][j] = f0; lv[1][j] = f1; lv[2][j] = f2; }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { p[0][j] = (float)lv[0][j]; p[1][j] = (float)lv[1][j]; p[2][j] = (float)lv[2][j]; }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        v[0][j] = (p[0][j] - m0) * r0;
+        v[1][j] = (p[1][j] - m1) * r1;
+        v[2][j] = (p[2][j] - m2) * r2;
+    }
+}
+
 __global__ __launch_bounds__(256) void image_prep_kernel(const unsigned char* __restrict__ src, const int* __restrict__ sizes,
                                                          const unsigned char* __restrict__ flags, float* __restrict__ out,
                                                          int B, int Hs, int Ws, int Ho, int Wo, float m0, float m1, float m2,
                                                          float r0, float r1, float r2, float fill, bool vec) {
-    const int* __restrict__ table = (const int*)(flags + (((size_t)B + 15) & ~(size_t)15));     // dereferenced only behind bit 2
-    const int padlv = (int)fminf(fmaxf(fill, 0.f), 255.f);
+    const int* __restrict__ table = (const int*)(flags + (((size_t)B + 15) & ~(size_t)15));     // dereferenced only behind bit 2 / 3
     const int xg = (Wo + 3) >> 2;                       // 4-pixel groups per row
     const long long total = (long long)B * Ho * xg;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int gx = (int)(i % xg);
         const int y = (int)((i / xg) % Ho);
         const int b = (int)(i / ((long long)xg * Ho));
-        const int h = sizes ? sizes[2 * b] : Hs, w = sizes ? sizes[2 * b + 1] : Ws;
-        const int top = (Ho - h) / 2, left = (Wo - w) / 2;
         const unsigned fl = flags ? flags[b] : 0u;
-        const int yf = (fl & 2u) ? Ho - 1 - y : y;
-        const int sy = yf - top;
-        const bool row_in = (unsigned)sy < (unsigned)h;
-        const unsigned char* row = src + ((size_t)b * Hs + (row_in ? sy : 0)) * Ws * 3;
-        // the 12 source bytes are loaded and turned into the plain path's values in straight-line code, exactly as without records;
-        // lanes of an image with a record (per lane: a wave can straddle two images) then redo the arithmetic from the bytes
-        int q[3][4];
-        bool in[4];
-        float p[3][4];                                  // the value Normalize sees: a level, or `fill` itself on the plain path
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int x = gx * 4 + j;
-            const int xf = (fl & 1u) ? Wo - 1 - x : x;
-            const int sx = xf - left;
-            in[j] = row_in && (unsigned)sx < (unsigned)w && x < Wo;
-            const unsigned char* px = row + (in[j] ? sx : 0) * 3;
-            q[0][j] = px[0]; q[1][j] = px[1]; q[2][j] = px[2];
-            p[0][j] = in[j] ? (float)q[0][j] : fill;
-            p[1][j] = in[j] ? (float)q[1][j] : fill;
-            p[2][j] = in[j] ? (float)q[2][j] : fill;
-        }
-        if (fl & 4u) {
+        // flag bit 3: words 10..15 of record b mix image b with a partner.  take = the pixels of the group that come from the
+        // partner (box), 0xF for a blend; an image is evaluated only where one of its pixels is used, so a box costs one evaluation
+        // per pixel but in the groups its vertical edges cut.  A partner outside [0, B), the image itself or an unknown mode: no mix.
+        int partner = b, mode = 0;
+        unsigned take = 0u;
+        float lam = 1.f, oml = 0.f;
+        if (fl & 8u) {
             const int* __restrict__ rec = table + (size_t)kRecWords * b;
-            const int mask = rec[0];
-            const float alpha = __int_as_float(rec[1]), offset = __int_as_float(rec[2]);
-            const float hue = __int_as_float(rec[3]), sat = __int_as_float(rec[4]), val = __int_as_float(rec[5]);
-            const bool bc = mask & 1, hsv = (mask & 2) && (hue != 0.f || sat != 0.f || val != 0.f);
-            int lv[3][4];
+            const int p = rec[10], md = rec[11];
+            if ((unsigned)p < (unsigned)B && p != b) {
+                if (md == 1) {
+                    partner = p; mode = 1; take = 0xFu;
+                    lam = __int_as_float(rec[12]); oml = __int_as_float(rec[13]);
+                } else if (md == 2) {
+                    const int y1 = rec[12], x1 = rec[13], y2 = rec[14], x2 = rec[15];
+                    if (y >= y1 && y < y2) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                int cr = in[j] ? q[0][j] : padlv, cg = in[j] ? q[1][j] : padlv, cb = in[j] ? q[2][j] : padlv;
-                if (bc) {
-                    cr = aug_brightness_contrast(cr, alpha, offset);
-                    cg = aug_brightness_contrast(cg, alpha, offset);
-                    cb = aug_brightness_contrast(cb, alpha, offset);
-                }
-                if (hsv) aug_hsv(cr, cg, cb, hue, sat, val);
-                lv[0][j] = cr; lv[1][j] = cg; lv[2][j] = cb;
-            }
-            if (mask & 4) {                             // CoarseDropout: boxes in output-canvas coordinates, half-open
-                const int n = min(max(rec[6], 0), kMaxHoles);
-                const int f0 = rec[7], f1 = rec[8], f2 = rec[9];
-                for (int k = 0; k < n; ++k) {
-                    const int y1 = rec[16 + 4 * k], x1 = rec[17 + 4 * k], y2 = rec[18 + 4 * k], x2 = rec[19 + 4 * k];
-                    if (y < y1 || y >= y2) continue;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int x = gx * 4 + j;
-                        if (x >= x1 && x < x2) { lv[0][j] = f0; lv[1][j] = f1; lv[2][j] = f2; }
+                        for (int j = 0; j < 4; ++j) {
+                            const int x = gx * 4 + j;
+                            if (x >= x1 && x < x2) take |= 1u << j;
+                        }
                     }
+                    if (take) { partner = p; mode = 2; }
                 }
             }
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { p[0][j] = (float)lv[0][j]; p[1][j] = (float)lv[1][j]; p[2][j] = (float)lv[2][j]; }
         }
         float v[3][4];
+        if (mode != 2 || take != 0xFu)
+            prep_group(src, sizes, table, b, fl, y, gx, Hs, Ws, Ho, Wo, m0, m1, m2, r0, r1, r2, fill, v);
+        if (mode) {
+            float u[3][4];
+            prep_group(src, sizes, table, partner, flags[partner], y, gx, Hs, Ws, Ho, Wo, m0, m1, m2, r0, r1, r2, fill, u);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            v[0][j] = (p[0][j] - m0) * r0;
-            v[1][j] = (p[1][j] - m1) * r1;
-            v[2][j] = (p[2][j] - m2) * r2;
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (mode == 1) {
+                        const float tb = lam * v[c][j], tp = oml * u[c][j];     // two multiplies and one add (no contraction)
+                        v[c][j] = tb + tp;
+                    } else if (take >> j & 1u) {
+                        v[c][j] = u[c][j];
+                    }
+                }
         }
         const size_t plane = (size_t)Ho * Wo;
         float* o = out + (size_t)b * 3 * plane + (size_t)y * Wo + gx * 4;

@@ -290,6 +290,82 @@ def draw_image_aug(gen, B, size, spec):
     return torch.from_numpy(bits), torch.from_numpy(rec)
 
 
+MIX_MODES = ("batch", "pair", "elem")
+_MIX_DEFAULTS = dict(mixup_alpha=1.0, cutmix_alpha=0.0, cutmix_minmax=None, prob=1.0, switch_prob=0.5, mode="batch",
+                     correct_lam=True)
+
+
+def normalise_mix_spec(spec):
+    """None, or a dict of timm.data.Mixup's argument names -> the same with defaults filled in; None when nothing can mix.
+    label_smoothing and num_classes are not taken here: smoothing belongs to the loss (`loss["label_smoothing"]`)."""
+    if spec is None:
+        return None
+    unknown = set(spec) - set(_MIX_DEFAULTS)
+    if unknown:
+        raise ValueError(f"mixup: unknown arguments {sorted(unknown)}; known: {sorted(_MIX_DEFAULTS)}")
+    out = {**_MIX_DEFAULTS, **spec}
+    if out["cutmix_minmax"] is not None:
+        raise NotImplementedError("mixup: cutmix_minmax is not built (boxes come from lam, as timm's rand_bbox draws them)")
+    if not out["correct_lam"]:
+        raise NotImplementedError("mixup: correct_lam=False is not built (lam is always corrected to the clipped box)")
+    if out["mode"] not in MIX_MODES:
+        raise ValueError(f"mixup: mode {out['mode']!r}; known: {MIX_MODES}")
+    if out["mixup_alpha"] < 0 or out["cutmix_alpha"] < 0 or not 0.0 <= out["prob"] <= 1.0 or not 0.0 <= out["switch_prob"] <= 1.0:
+        raise ValueError(f"mixup: need alphas >= 0 and probabilities in [0, 1], got {out!r}")
+    if out["mixup_alpha"] == 0 and out["cutmix_alpha"] == 0:
+        return None
+    return out
+
+
+def draw_batch_mix(rng, B, size, spec):
+    """The Mixup / CutMix draws of one batch (timm.data.Mixup's rules restated from memory: parity UNPINNED) ->
+    (bits uint8 [B]: 8 where the image is mixed, words int32 [B, 6]: words 10..15 of its record, partner int64 [B],
+    lam float64 [B]: the weight of the image's own label).
+
+    rng: numpy Generator.  Image b's partner is B - 1 - b.  A unit is the batch ("batch"), a pair (b, B - 1 - b) ("pair") or an
+    image ("elem"); n units draw, in this order and whatever they decide: rng.random((n, 2)) [apply, switch], rng.beta(mixup_alpha,
+    mixup_alpha, n) if mixup_alpha > 0, rng.beta(cutmix_alpha, cutmix_alpha, n) if cutmix_alpha > 0, rng.integers(0, size, (n, 2))
+    [cy, cx].  A unit mixes where apply < prob; with both alphas set it cuts where switch < switch_prob.  Blend: lam is the
+    float32 of the draw (what the record holds).  Box (rand_bbox): cut = int(size * sqrt(1 - lam)), edges clip(c -+ cut // 2, 0, size),
+    lam corrected to 1 - area / size^2.  An image that is its own partner, a unit that does not mix and a box without area leave
+    the image unmixed: lam = 1, words zero, no bit."""
+    from .hip import IMAGE_MIX_BIT, IMAGE_MIX_BLEND, IMAGE_MIX_BOX
+    spec = normalise_mix_spec(spec)
+    bits, words = np.zeros(B, np.uint8), np.zeros((B, 6), np.int32)
+    partner, lam = B - 1 - np.arange(B, dtype=np.int64), np.ones(B, np.float64)
+    if spec is None or B == 0:
+        return torch.from_numpy(bits), torch.from_numpy(words), torch.from_numpy(partner), torch.from_numpy(lam)
+    mode, ma, ca = spec["mode"], float(spec["mixup_alpha"]), float(spec["cutmix_alpha"])
+    n = 1 if mode == "batch" else (B + 1) // 2 if mode == "pair" else B
+    u = rng.random((n, 2))
+    lam_mix = rng.beta(ma, ma, n) if ma > 0 else None
+    lam_cut = rng.beta(ca, ca, n) if ca > 0 else None
+    centre = rng.integers(0, size, (n, 2))
+    idx = np.arange(B)
+    unit = np.zeros(B, np.int64) if mode == "batch" else np.minimum(idx, B - 1 - idx) if mode == "pair" else idx
+    apply = u[unit, 0] < spec["prob"]
+    cut = (u[unit, 1] < spec["switch_prob"]) if (ma > 0 and ca > 0) else np.full(B, ca > 0)
+    # box of every image, from its unit's cut draw
+    raw = (lam_cut if lam_cut is not None else np.ones(n))[unit]
+    ext = (size * np.sqrt(1.0 - raw)).astype(np.int64)
+    cy, cx = centre[unit, 0], centre[unit, 1]
+    y1, y2 = np.clip(cy - ext // 2, 0, size), np.clip(cy + ext // 2, 0, size)
+    x1, x2 = np.clip(cx - ext // 2, 0, size), np.clip(cx + ext // 2, 0, size)
+    area = (y2 - y1) * (x2 - x1)
+    blend = (lam_mix if lam_mix is not None else np.ones(n))[unit].astype(np.float32)
+    mixed = apply & (partner != idx) & np.where(cut, area > 0, True)
+    box, mix = mixed & cut, mixed & ~cut
+    lam = np.where(box, 1.0 - area / float(size * size), np.where(mix, blend.astype(np.float64), 1.0))
+    bits[mixed] = IMAGE_MIX_BIT
+    words[:, 0] = np.where(mixed, partner, 0)
+    words[:, 1] = np.where(box, IMAGE_MIX_BOX, np.where(mix, IMAGE_MIX_BLEND, 0))
+    f = words.view(np.float32)
+    f[mix, 2] = blend[mix]
+    f[mix, 3] = np.float32(1.0) - blend[mix]
+    words[box, 2:6] = np.stack([y1, x1, y2, x2], 1)[box]
+    return torch.from_numpy(bits), torch.from_numpy(words), torch.from_numpy(partner), torch.from_numpy(lam)
+
+
 # transforms of the reference stack, in the only order the kernel applies them
 _PIPELINE_ORDER = ("LongestMaxSize", "PadIfNeeded", "HorizontalFlip", "VerticalFlip", "RandomBrightnessContrast",
                    "HueSaturationValue", "CoarseDropout", "Normalize", "ToTensorV2")
@@ -347,10 +423,17 @@ class DeviceLoader:
     brightness_contrast / hue_saturation_value / coarse_dropout: None or a dict of albumentations' argument names plus `p`
     (normalise_aug_spec).  Their draws (draw_image_aug) come from a SECOND generator seeded `seed + 1`, never from the flip
     generator; the records ride behind the flag bytes (hip.pack_image_aug) on the copy stream.  With all three None nothing
-    changes: same draws, same buffers."""
+    changes: same draws, same buffers.
+
+    mixup: None or a dict of timm.data.Mixup's argument names (normalise_mix_spec).  Its draws (draw_batch_mix) come from a
+    THIRD generator, numpy's default_rng(seed + 2); the mixing instructions ride in words 10..15 of the records, the image is
+    mixed inside the prep launch, and the target of a batch with a mixed image becomes a losses.MixedTarget (a dict of them
+    for dict targets: one lam and one partner shared by all tasks) uploaded with the batch.  A batch without a mixed image keeps
+    its plain labels.  With mixup None nothing changes: same draws, same buffers."""
 
     def __init__(self, loader, device, size, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), hflip_p=0.0,
-                 vflip_p=0.0, fill=0.0, seed=0, brightness_contrast=None, hue_saturation_value=None, coarse_dropout=None):
+                 vflip_p=0.0, fill=0.0, seed=0, brightness_contrast=None, hue_saturation_value=None, coarse_dropout=None,
+                 mixup=None):
         self.loader, self.device = loader, torch.device(device)
         self.size, self.mean, self.std, self.fill = size, tuple(mean), tuple(std), float(fill)
         self.hflip_p, self.vflip_p = float(hflip_p), float(vflip_p)
@@ -358,6 +441,8 @@ class DeviceLoader:
         self.aug = normalise_aug_spec(dict(brightness_contrast=brightness_contrast, hue_saturation_value=hue_saturation_value,
                                            coarse_dropout=coarse_dropout))
         self.aug_gen = torch.Generator().manual_seed(seed + 1)
+        self.mixup = normalise_mix_spec(mixup)
+        self.mix_rng = np.random.default_rng(seed + 2)
         self.dataset = getattr(loader, "dataset", None)
         self._copy = None
 
@@ -366,16 +451,40 @@ class DeviceLoader:
 
     def draw_flags(self, B):
         """The host draws of one batch -> what nkb_image_prep takes as `flags`: None, uint8 [B] flip bits (one torch.rand(B, 2)
-        from the flip generator), or, with augmentations on, those bits | the record bits with the record table behind them."""
+        from the flip generator), or, with augmentations or mixup on, those bits | the record bits with the record table behind
+        them."""
+        return self._draw(B)[0]
+
+    def _draw(self, B):
+        """(flags as draw_flags returns them, None or the (partner int64 [B], lam float64 [B]) of a batch with a mixed image)"""
         flags = None
         if self.hflip_p > 0 or self.vflip_p > 0:
             u = torch.rand(B, 2, generator=self.gen)
             flags = ((u[:, 0] < self.hflip_p).to(torch.uint8) | ((u[:, 1] < self.vflip_p).to(torch.uint8) << 1))
+        bits = records = mix = None
         if self.aug is not None:
-            from . import hip
             bits, records = draw_image_aug(self.aug_gen, B, self.size, self.aug)
+        if self.mixup is not None:
+            from .hip import IMAGE_AUG_WORDS
+            mbits, words, partner, lam = draw_batch_mix(self.mix_rng, B, self.size, self.mixup)
+            if records is None:
+                bits, records = torch.zeros(B, dtype=torch.uint8), torch.zeros(B, IMAGE_AUG_WORDS, dtype=torch.int32)
+            records[:, 10:16] = words
+            bits = bits | mbits
+            if bool(mbits.any()):
+                mix = (partner, lam)
+        if records is not None:
+            from . import hip
             flags = hip.pack_image_aug(bits if flags is None else flags | bits, records)
-        return flags
+        return flags, mix
+
+    @staticmethod
+    def _mixed_target(labels, mix):
+        """labels [B] and the batch's (partner, lam) -> the host table of a MixedTarget"""
+        from .losses import MixedTarget
+        partner, lam = mix
+        y = torch.as_tensor(labels).to(torch.int64).reshape(-1)
+        return MixedTarget.build(y, y[partner], lam)
 
     def _stage(self, item):
         """Pinned host batch -> device uint8 on the copy stream; returns what the compute stream needs."""
@@ -385,7 +494,12 @@ class DeviceLoader:
             (raw, target), sizes = item, None
         if raw.dtype != torch.uint8 or raw.dim() != 4 or raw.shape[-1] != 3:
             raise RuntimeError(f"DeviceLoader expects uint8 [B,H,W,3] batches, got {tuple(raw.shape)} {raw.dtype}")
-        flags = self.draw_flags(raw.shape[0])
+        flags, mix = self._draw(raw.shape[0])
+        if mix is not None:
+            if isinstance(target, dict):
+                target = {k: self._mixed_target(v, mix).pin_memory() for k, v in target.items()}
+            else:
+                target = self._mixed_target(target, mix).pin_memory()
         if self._copy is None:
             self._copy = torch.cuda.Stream(device=self.device)
         pin = lambda t: t if t is None or t.is_pinned() else t.contiguous().pin_memory()       # noqa: E731
@@ -395,12 +509,13 @@ class DeviceLoader:
             d_sizes = sizes.to(self.device, non_blocking=True) if sizes is not None else None
             d_flags = flags.to(self.device, non_blocking=True) if flags is not None else None
             if isinstance(target, dict):
-                d_target = {k: torch.as_tensor(v).to(self.device, non_blocking=True) for k, v in target.items()}
+                d_target = {k: (v if mix is not None else torch.as_tensor(v)).to(self.device, non_blocking=True)
+                            for k, v in target.items()}
             else:
-                d_target = torch.as_tensor(target).to(self.device, non_blocking=True)
+                d_target = (target if mix is not None else torch.as_tensor(target)).to(self.device, non_blocking=True)
             ready = torch.cuda.Event()
             ready.record(self._copy)
-        return dict(raw=d_raw, sizes=d_sizes, flags=d_flags, target=d_target, ready=ready, host=(raw, sizes, flags))
+        return dict(raw=d_raw, sizes=d_sizes, flags=d_flags, target=d_target, ready=ready, host=(raw, sizes, flags, target))
 
     def _finish(self, st):
         from . import hip
@@ -438,7 +553,8 @@ class DeviceLoader:
 def get_dataset(data, pipeline=None):
     """dataset.py:541-629.  Extra keys: `device_pipeline=True` (+ `device`, `hflip_p`, `vflip_p`, `mean`, `std`) wraps the
     folder loader in a DeviceLoader; `rank` / `world` (+ `shard_seed`, the seed of the permutation all ranks share) shard the data for one-process-per-GPU
-    training.  With `device_pipeline` the keys `brightness_contrast`, `hue_saturation_value`, `coarse_dropout` (None or a dict of
+    training.  `mixup` (None or a dict of timm.data.Mixup's argument names: mixup_alpha, cutmix_alpha, prob, switch_prob, mode) mixes
+    the batch inside the device pipeline and needs `device_pipeline`.  With `device_pipeline` the keys `brightness_contrast`, `hue_saturation_value`, `coarse_dropout` (None or a dict of
     albumentations' argument names plus `p`) and `fill` go to the DeviceLoader too, and a `pipeline` that has a `.transforms`
     list is translated into all of these keys (translate_pipeline); explicit `data` keys win over the translated ones."""
     kind = data.get("type", "folder")
@@ -446,6 +562,8 @@ def get_dataset(data, pipeline=None):
     if on_device and isinstance(getattr(pipeline, "transforms", None), (list, tuple)):
         data = {**translate_pipeline(pipeline), **data}
     size = data.get("size", 224)
+    if data.get("mixup") is not None and not (on_device and kind != "synthetic"):
+        raise NotImplementedError("mixup is built into the device pipeline only: set device_pipeline=True on a folder dataset")
     if kind == "synthetic":
         ds = SyntheticDataset(data["n_images"], data["classes"], size=size, seed=data.get("seed", 1234))
         on_device = False
@@ -469,5 +587,5 @@ def get_dataset(data, pipeline=None):
         return DeviceLoader(loader, data.get("device", "cuda:0"), size, mean=data.get("mean", (0.485, 0.456, 0.406)),
                             std=data.get("std", (0.229, 0.224, 0.225)), hflip_p=data.get("hflip_p", 0.0),
                             vflip_p=data.get("vflip_p", 0.0), fill=data.get("fill", 0.0), seed=data.get("seed", 0),
-                            **{k: data.get(k) for k in AUG_KEYS})
+                            **{k: data.get(k) for k in AUG_KEYS}, mixup=data.get("mixup"))
     return loader

@@ -18,6 +18,7 @@ import torch
 from tqdm import tqdm
 
 from . import hip
+from .losses import MixedTarget
 
 
 class TrainPbar(tqdm):
@@ -78,13 +79,21 @@ def _upload(target, device):
     return target.to(device, non_blocking=True)
 
 
+def _primary(target):
+    """What the logger takes as ground truth: the labels, for a MixedTarget (a mixed batch of the device pipeline) its own
+    labels y — the image's, not the partner's."""
+    if isinstance(target, dict):
+        return {name: _primary(labels) for name, labels in target.items()}
+    return target.y if isinstance(target, MixedTarget) else target
+
+
 def _forward_and_loss(model, criterion, img, target, device, cfg):
     """engine.py:43-51: autocast region around model(img) and criterion(preds, target)."""
     if hasattr(model, "fp8_linear"):
         model.fp8_linear = bool(cfg.enable_mixed_presicion and getattr(cfg, "amp_dtype", None) == "fp8")
     with torch.autocast(device_type="cuda", dtype=_amp_dtype(cfg), enabled=cfg.enable_mixed_presicion):
         preds = model(img)
-        labels = _upload(target, device) if isinstance(target, torch.Tensor) else target
+        labels = _upload(target, device) if isinstance(target, (torch.Tensor, MixedTarget)) else target
         return preds, labels, criterion(preds, labels)
 
 
@@ -103,7 +112,7 @@ def train_epoch(model, train_loader, optimizer, scheduler, scaler, criterion, de
         scaler.scale(total).backward()
         scaler.step(optimizer)
         scaler.update()
-        epoch_logger.log_iter(preds, _upload(target, device) if isinstance(target, dict) else target, loss)
+        epoch_logger.log_iter(preds, _primary(_upload(target, device) if isinstance(target, dict) else target), loss)
         if grad_log is not None:
             _grad_norms(model, grad_log)
         epoch_logger.log_images_if_needed(img)

@@ -744,14 +744,25 @@ def pad_cast(dtype, src, dst, rows, C_, ld_src, ld_dst, mul=1.0):
     check(load().nkb_pad_cast(dtype, ptr(src), ptr(dst), rows, C_, ld_src, ld_dst, mul, stream()), "pad_cast")
 
 
+LOSS_MIXED = 16                     # NKB_LOSS_MIXED of nkbhip.h: kind | 16 is the two-label form of kind 0 / 1
+
+
+def loss_mixed_state_bytes(B, C_):
+    """row_state of a mixed launch: 32 bytes per row, then the C floats ew[j] (layout in nkbhip.h)"""
+    return 32 * B + 4 * C_
+
+
 def loss_forward(kind, logits, ld, target, B, C_, class_weight, gamma, ignore_index, probs, ldp, argmax, row_state, out2,
                  reduction=0):
+    """kind | LOSS_MIXED: target is the int64 table [3][B] (y, y2, float64 bits of lam), row_state loss_mixed_state_bytes(B, C)
+    long, and for kind 0 `gamma` carries the label-smoothing eps"""
     check(load().nkb_loss_forward(kind, ptr(logits), ld, ptr(target), B, C_, ptr(class_weight), gamma, ignore_index,
                                   ptr(probs), ldp, ptr(argmax), ptr(row_state), ptr(out2), reduction, stream()),
           "loss_forward")
 
 
 def loss_backward(probs, ldp, target, row_state, out2, grad_out, B, C_, dlogits, ldd, per_row=False):
+    """per_row is the bit field of nkbhip.h: bit 0 one grad_out per row, bit 1 (value 2) the records and target of a mixed forward"""
     check(load().nkb_loss_backward(ptr(probs), ldp, ptr(target), ptr(row_state), ptr(out2), ptr(grad_out), int(per_row), B,
                                    C_, ptr(dlogits), ldd, stream()), "loss_backward")
 
@@ -936,6 +947,7 @@ def wfold(dtype, w, scale, dst, Cout, K):
 
 
 IMAGE_AUG_BIT, IMAGE_AUG_WORDS, IMAGE_AUG_MAX_HOLES = 4, 64, 12     # flag bit 2, words per record, boxes per record (nkbhip.h)
+IMAGE_MIX_BIT, IMAGE_MIX_BLEND, IMAGE_MIX_BOX = 8, 1, 2             # flag bit 3: words 10..15 of the record mix the image (nkbhip.h)
 
 
 def image_aug_bytes(B):
@@ -946,13 +958,21 @@ def image_aug_bytes(B):
 def pack_image_aug(flags, records):
     """flags uint8 [B] (bit 0 / 1 flips, bit 2 = IMAGE_AUG_BIT: this image has a record), records int32 [B, 64] (host tensors)
     -> the uint8 buffer nkb_image_prep reads when a bit 2 is set: flags, zero pad to 16 bytes, the record table.  Pinned when
-    both inputs are pinned.  The kernel reads record b only where flags[b] has bit 2, whatever the other records hold."""
+    both inputs are pinned.  The kernel reads record b only where flags[b] has bit 2, whatever the other records hold, and
+    words 10..15 only where it has bit 3 (IMAGE_MIX_BIT): there word 10 must be a partner index in [0, B) and word 11 a mode."""
     B = flags.numel()
     if flags.dtype != torch.uint8 or records.dtype != torch.int32 or tuple(records.shape) != (B, IMAGE_AUG_WORDS):
         raise RuntimeError(f"pack_image_aug: expected uint8 [B] flags and int32 [B, {IMAGE_AUG_WORDS}] records, got "
                            f"{tuple(flags.shape)} {flags.dtype} and {tuple(records.shape)} {records.dtype}")
     if flags.is_cuda or records.is_cuda:
         raise RuntimeError("pack_image_aug: packs host tensors (the buffer then crosses with the batch)")
+    mixed = (flags.reshape(-1) & IMAGE_MIX_BIT) != 0
+    if bool(mixed.any()):
+        partner, mode = records[mixed, 10], records[mixed, 11]
+        if bool(((partner < 0) | (partner >= B)).any()):
+            raise RuntimeError(f"pack_image_aug: a partner index (word 10) lies outside [0, {B})")
+        if bool(((mode != IMAGE_MIX_BLEND) & (mode != IMAGE_MIX_BOX)).any()):
+            raise RuntimeError("pack_image_aug: a mix mode (word 11) is neither 1 (blend) nor 2 (box)")
     off = (B + 15) // 16 * 16
     buf = torch.zeros(image_aug_bytes(B), dtype=torch.uint8, pin_memory=flags.is_pinned() and records.is_pinned())
     buf[:B] = flags.reshape(-1)
