@@ -96,6 +96,24 @@ int nkb_conv_wgrad_assign(int dtype, const void* dy, const void* x, float* dw, f
  * split order.  workspace == NULL keeps the single-launch form that accumulates with fp32 atomics. */
 long long nkb_conv_wgrad_workspace_floats(int dtype, int N, int P, int Q, int Cin, int Cout, int R, int S, int stride, int pad,
                                           int has_bias);
+/* Which weight-gradient kernel the last launch of nkb_conv_wgrad / nkb_conv_wgrad_assign / nkb_stem_wgrad / nkb_gemm_tn_batched took
+ * and which reduce kernel ran last (tests prove with it that every kernel and every reduce path is reached).  -1 before any launch.
+ *   bits 0-1  family: NKB_WGRAD_GENERIC conv_wgrad_kernel<T>, NKB_WGRAD_3X3 wgrad3x3p_kernel<PWS, 3>, NKB_WGRAD_R wgradr_kernel,
+ *             NKB_WGRAD_8P wgrad8p_kernel
+ *   bits 4-7  the family's variant — generic: bit 4 bf16 (else fp32), bit 5 the direct store in the compute dtype
+ *             (nkb_gemm_tn_batched); wgrad3x3: PWS (3 .. 6); wgradr: bit 4 the wide form <2, 8> (else <3, 4>), bit 5 transposed
+ *             (the 256-channel tiles on X)
+ *   bit 8     slab form (a workspace was given; else fp32 atomics, or the direct store)
+ *   bits 9-11 the reduce kernel launched last: 0 none since the weight-gradient launch, 1 / 2 / 3 wgrad_reduce_kernel<1 / 4 / 16>,
+ *             4 wgrad_reduce_scalar_kernel;  bit 12: it assigned (else accumulated);  bit 13: it reduced two ranges in one launch
+ *   bits 16.. the split count of the weight-gradient launch
+ * One host-side store per launch.  A weight-gradient launch rewrites the whole value (reduce bits 0); a reduce launch rewrites bits
+ * 9-13 only — the reducer also serves other families (column sums, depthwise and stem gradients), whose launches show here too. */
+#define NKB_WGRAD_GENERIC 0
+#define NKB_WGRAD_3X3 1
+#define NKB_WGRAD_R 2
+#define NKB_WGRAD_8P 3
+int nkb_wgrad_last_kernel(void);
 
 /* BatchNorm2d (torch semantics: biased var to normalise, unbiased var into running_var, momentum blend). */
 int nkb_bn_finalize(const float* partials, int tiles, int C, long long count, const float* gamma, const float* beta,

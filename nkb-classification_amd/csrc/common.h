@@ -190,6 +190,8 @@ int nkb_launch_wgrad_reduce(const float* part, long long slab, int splits, float
 // the same for two ranges in ONE launch (weight slabs + the bias partials behind them)
 int nkb_launch_wgrad_reduce2(const float* part, long long slab, int splits, float* dst, long long n, const float* part2, long long slab2,
                              float* dst2, long long n2, bool assign, hipStream_t stream);
+// records what nkb_wgrad_last_kernel answers (conv_igemm.hip): family NKB_WGRAD_*, its variant (bits 4-7 of the code), slab form, splits
+void nkb_wgrad_note_kernel(int family, int variant, bool slabs, int splits);
 
 // the global-response-normalisation passes of nkb_avgpool (csrc/grn.hip): modes NKB_GRN_* of include/nkbhip.h
 int nkb_grn(int dtype, int mode, const void* in, void* out, int N, int HW, int C, const void* in2, const float* weight, const float* bias,

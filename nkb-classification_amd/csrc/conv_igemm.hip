@@ -1176,6 +1176,16 @@ __global__ void wgrad_reduce_scalar_kernel(const float* __restrict__ part, long 
         dst[i] = assign ? a : dst[i] + a;
     }
 }
+// nkb_wgrad_last_kernel (include/nkbhip.h): the weight-gradient kernel launched last and the reduce kernel launched last
+static int g_wgrad_last_kernel = -1;
+void nkb_wgrad_note_kernel(int family, int variant, bool slabs, int splits) {
+    g_wgrad_last_kernel = (family & 3) | (variant & 15) << 4 | (int)slabs << 8 | splits << 16;
+}
+// kind: 1 / 2 / 3 wgrad_reduce_kernel<1 / 4 / 16>, 4 the scalar kernel
+static void wgrad_note_reduce(int kind, bool assign, bool two_ranges) {
+    if (g_wgrad_last_kernel >= 0) g_wgrad_last_kernel = (g_wgrad_last_kernel & ~(31 << 9)) | kind << 9 | (int)assign << 12 | (int)two_ranges << 13;
+}
+extern "C" int nkb_wgrad_last_kernel(void) { return g_wgrad_last_kernel; }
 template <bool ASSIGN>
 static void launch_wgrad_reduce_kernel(int sg, unsigned grid, hipStream_t stream, const float* part, long long slab, int splits, float* dst,
                                        long long n, const float* part2, long long slab2, float* dst2, long long n2) {
@@ -1191,6 +1201,7 @@ int nkb_launch_wgrad_reduce(const float* part, long long slab, int splits, float
         long long g = (n + 255) / 256;
         if (g > 4096) g = 4096;
         hipLaunchKernelGGL(wgrad_reduce_scalar_kernel, dim3((unsigned)g), dim3(256), 0, stream, part, slab, splits, dst, n, assign ? 1 : 0);
+        wgrad_note_reduce(4, assign, false);
         return nkb_check_launch("wgrad_reduce");
     }
     const long long n4 = n >> 2;
@@ -1201,6 +1212,7 @@ int nkb_launch_wgrad_reduce(const float* part, long long slab, int splits, float
     if (grid < 1) grid = 1;
     if (assign) launch_wgrad_reduce_kernel<true>(sg, (unsigned)grid, stream, part, slab, splits, dst, n, nullptr, 0, nullptr, 0);
     else launch_wgrad_reduce_kernel<false>(sg, (unsigned)grid, stream, part, slab, splits, dst, n, nullptr, 0, nullptr, 0);
+    wgrad_note_reduce(sg == 16 ? 3 : sg == 4 ? 2 : 1, assign, false);
     return nkb_check_launch("wgrad_reduce");
 }
 // two ranges in one launch (weight slabs + bias partials of one weight gradient); falls back to two launches where the vector form
@@ -1221,6 +1233,7 @@ int nkb_launch_wgrad_reduce2(const float* part, long long slab, int splits, floa
     if (grid > 4096) grid = 4096;
     if (assign) launch_wgrad_reduce_kernel<true>(sg, (unsigned)grid, stream, part, slab, splits, dst, n, part2, slab2, dst2, n2);
     else launch_wgrad_reduce_kernel<false>(sg, (unsigned)grid, stream, part, slab, splits, dst, n, part2, slab2, dst2, n2);
+    wgrad_note_reduce(sg == 16 ? 3 : sg == 4 ? 2 : 1, assign, true);
     return nkb_check_launch("wgrad_reduce");
 }
 
@@ -1676,6 +1689,7 @@ static int launch_conv_wgrad(const WgradParams& p, int dtype, dim3 grid, hipStre
     }
     if (dtype == NKB_DT_BF16) hipLaunchKernelGGL(conv_wgrad_kernel<bf16_t>, grid, dim3(256), lds, stream, p);
     else hipLaunchKernelGGL(conv_wgrad_kernel<float>, grid, dim3(256), lds, stream, p);
+    nkb_wgrad_note_kernel(NKB_WGRAD_GENERIC, (int)(dtype == NKB_DT_BF16) | (int)(p.out_t != nullptr) << 1, p.part != nullptr, p.splits);
     return nkb_check_launch(name);
 }
 

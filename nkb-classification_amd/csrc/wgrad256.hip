@@ -507,6 +507,7 @@ int nkb_launch_wgrad256(const void* dy, const void* x, float* dw, float* dbias, 
     }
     nkb_count_launch(NKB_LAUNCH_WGRAD8P);
     hipLaunchKernelGGL(wgrad8p_kernel, dim3((unsigned)tiles * (unsigned)p.splits), dim3(512), lds, stream, p);
+    nkb_wgrad_note_kernel(NKB_WGRAD_8P, 0, workspace != nullptr, p.splits);
     int rc = nkb_check_launch("wgrad256");
     if (rc || !workspace) return rc;
     rc = nkb_launch_wgrad_reduce(workspace, p.slab, p.splits, dw, p.slab, assign, stream);

@@ -323,6 +323,7 @@ int nkb_launch_wgrad3x3(const void* dy, const void* x, float* dw, int N, int H, 
         case 5: w3p_launch<5, 3>(p, stream); break;
         default: w3p_launch<6, 3>(p, stream); break;
     }
+    nkb_wgrad_note_kernel(NKB_WGRAD_3X3, p.pw_shift, workspace != nullptr, p.splits);
     int rc = nkb_check_launch("wgrad3x3");
     if (rc || !workspace) return rc;
     return nkb_launch_wgrad_reduce(workspace, p.slab, p.splits, dw, p.slab, assign, stream);

@@ -319,6 +319,7 @@ int nkb_launch_wgradr(const void* dy, const void* x, float* dw, float* dbias, lo
     p.M = (int)M; p.ldw = Cin; p.tilesG = g.tilesG; p.tilesA = g.tilesA; p.splits = g.splits; p.rows_per_split = g.rows;
     p.transposed = g.transposed;
     if (g.wide) wr_launch<2, 8>(p, stream); else wr_launch<3, 4>(p, stream);
+    nkb_wgrad_note_kernel(NKB_WGRAD_R, g.wide | g.transposed << 1, workspace != nullptr, g.splits);
     int rc = nkb_check_launch("wgradr");
     if (rc || !workspace) return rc;
     if (dbias) return nkb_launch_wgrad_reduce2(workspace, p.slab, g.splits, dw, p.slab, p.bpart, Cout, dbias, Cout, assign, stream);

@@ -441,6 +441,12 @@ def conv_wgrad_workspace(dtype, *, N, P, Q, Cin, Cout, R=1, S=1, stride=1, pad=0
     return int(load().nkb_conv_wgrad_workspace_floats(dtype, N, P, Q, Cin, Cout, R, S, stride, pad, int(has_bias)))
 
 
+def wgrad_last_kernel() -> int:
+    """The weight-gradient kernel of the last conv_wgrad / stem_wgrad / gemm_tn_batched launch and the reduce kernel launched last
+    (encoding: nkb_wgrad_last_kernel in include/nkbhip.h); -1 before any launch."""
+    return int(load().nkb_wgrad_last_kernel())
+
+
 def stem_wgrad_workspace(dtype, N, H, W, Cout) -> int:
     return int(load().nkb_stem_wgrad_workspace_floats(dtype, N, H, W, Cout))
 

@@ -116,14 +116,14 @@ def test_derived_signature_equals_pinned_literal(name):
 def test_pure_is_declared_without_a_stream():
     """hip._PURE (called, never recorded into a launch plan) = the entry points whose prototype has no nkb_stream_t parameter."""
     for name in ("nkb_stem3_tiles", "nkb_gemm8p_config", "nkb_plan_run", "nkb_kernel_name", "nkb_bn_stats_floats", "nkb_last_error",
-                 "nkb_conv_last_instance"):
+                 "nkb_conv_last_instance", "nkb_wgrad_last_kernel"):
         assert name in hip._PURE, name
     for name in ("nkb_stem3_conv", "nkb_bn_apply", "nkb_dropout", "nkb_optim_step", "nkb_fp8_scale_update"):
         assert name not in hip._PURE, name
     text = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "nkbhip.h").read_text(), flags=re.S)
     protos = dict(re.findall(r"\b(nkb_[a-z0-9_]+)\s*\(([^;{]*?)\)\s*;", text, flags=re.S))
     assert hip._PURE == frozenset(n for n, params in protos.items() if "nkb_stream_t" not in params)
-    assert isinstance(hip._PURE, frozenset) and len(hip._PURE) == 44 and len(hip._SIGS) == 124
+    assert isinstance(hip._PURE, frozenset) and len(hip._PURE) == 45 and len(hip._SIGS) == 125
 
 
 _LAUNCH_COUNTERS = {"gemm8p": 0, "wgrad8p": 1, "wgrad3x3": 2, "wgrad8f": 3, "gram_conv": 4, "gram_bn_apply": 5, "convp": 6, "conv1p": 7,

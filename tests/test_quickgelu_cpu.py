@@ -128,7 +128,7 @@ def _linear_gelu(act, y2=None, M=64, K=64, N=64):
 
 def test_new_act_codes_and_kinds_are_validated_on_the_host():
     lib = hip.load()
-    assert len(hip._SIGS) == 124 and len(hip._PURE) == 44
+    assert len(hip._SIGS) == 125 and len(hip._PURE) == 45
     assert len(hip._SIGS["nkb_linear_gelu"][1]) == 12
     assert len(hip._SIGS["nkb_gelu"][1]) == 7 and len(hip._SIGS["nkb_gelu_fwd_dgelu"][1]) == 7
     inside, outside = (50432, 768, 3072), (200, 128, 192)
