@@ -547,7 +547,41 @@ int nkb_wfold(int dtype, const float* w, const float* scale, void* dst, int Cout
  *   box:   out[b] = plain(p) inside the box, plain(b) outside.
  * p == b is a no-op (out[b] = plain(b), also for a blend); so is a partner outside [0, B) or a mode other than 1 or 2, which
  * hip.pack_image_aug refuses on the host.  The kernel reads only src through a partner.  Flag values 0..7 give the bits they gave
- * before bit 3 existed. */
+ * before bit 3 existed.
+ *
+ * Geometry records (RandomResizedCrop, MotionBlur and PadIfNeeded's BORDER_REFLECT_101 inside the same launch).  Flag bit 4
+ * (value 16): image b has a geometry record.  When ANY flag byte has bit 4 a SECOND table follows the first: it starts at byte
+ * offset roundup(B, 16) + 256 B — the 256-byte record table is then always present, zero-filled where unused — with record b at
+ * + 64 b, 16 little-endian 32-bit words each (hip.pack_image_geom keeps the layout).  The kernel reads geometry record k only where
+ * flags[k] has bit 4 (k = b, or b's mixing partner).  Words (f = float32 bits):
+ *   0      mask: bit 0 resample, bit 1 blur, bit 2 reflect-101 border in the pad stage
+ *   1..4   crop box y0, x0, bh, bw in image b's own source coordinates: 0 <= y0, y0 + bh <= h_b, bh >= 1, likewise x.  The host
+ *          guarantees this; the kernel clamps its reads so that a bad box cannot read outside image b's Hs x Ws slot
+ *   5 f, 6 f   sy = float32(bh) / float32(Ho), sx = float32(bw) / float32(Wo), divided on the host
+ *   7      number of blur taps n, clamped to 1..16
+ *   8..15  taps: tap t in the 16-bit half t % 2 of word 8 + t / 2, low byte dy, high byte dx, both signed 8-bit
+ * An image with a geometry record goes through uint8 LEVELS like an image with an augmentation record (pad level
+ * clamp((int)fill, 0, 255)); there is no fp32 division and no transcendental on the device.  Its canvas level in front of the colour
+ * stages is defined in three steps:
+ *   1. stage canvas C(y, x), 0 <= y < Ho, 0 <= x < Wo.
+ *      Resample (mask bit 0): the box is stretched over the whole canvas, no pad.  Per axis, with n the box extent, s the record's
+ *      scale and X the canvas coordinate: f = (float(X) + 0.5f) * s - 0.5f in three fp32 operations, i = floor(f), t = f - i;
+ *      i < 0: i = 0, t = 0; i >= n - 1: i = n - 1, t = 0; i' = min(i + 1, n - 1); c1 = (int)rintf(t * 2048.f), c0 = 2048 - c1;
+ *      level = (sum over a, b in {0, 1} of cy_a cx_b P[y0 + iy_a][x0 + ix_b] + 2^21) >> 22 per channel in 32-bit integers (at most
+ *      255 * 2^22 + 2^21).  bh == Ho gives (X, 2048, 0): a same-size box is the identity.
+ *      Otherwise the pad stage as without a record: the h_b x w_b image centred, top = (Ho - h) / 2, left = (Wo - w) / 2 in C integer
+ *      division (negative for an image larger than the canvas: its centred window).  Outside the image: the pad level, or with mask
+ *      bit 2 the source pixel at the reflect-101 index per axis.  reflect-101 with n the extent of the axis reflected in: i < 0 ->
+ *      -i, i >= n -> 2 (n - 1) - i, repeated until in range; n == 1 -> 0.
+ *   2. flips: F(y, x) = C(yf, xf), bits 0 and 1 as above.
+ *   3. blur (mask bit 1): level = (2 sum_t F(r(y + dy_t, Ho), r(x + dx_t, Wo)) + n) / (2 n) in integer division per channel, r =
+ *      reflect-101 at the canvas edge (filter2D's default border); pad pixels take part.
+ * The levels then continue through steps 2..5 of the augmentation record where flags[k] has bit 2, through Normalize otherwise.
+ * plain(k) of the mixing contract includes k's geometry record.  Flag values 0..15 and flags == NULL give the bits they gave before
+ * bit 4 existed.
+ * Sizes: with flags == NULL the source must fit the output (Hs <= Ho, Ws <= Wo) or the call is refused; with flags the source
+ * canvas may be larger, so that a crop box can cut from more pixels than it writes, and every image without the resample bit shows
+ * the centred window defined in step 1. */
 int nkb_image_prep(const unsigned char* src, const int* sizes, const unsigned char* flags, float* out, int B, int Hs, int Ws,
                    int Ho, int Wo, const float* mean, const float* stdev, float fill, nkb_stream_t stream);
 /* out = keep ? in/(1-p) : 0 (+ add); forward draws keep from a hash of (seed, index) and stores it in mask */

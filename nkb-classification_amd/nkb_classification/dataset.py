@@ -11,6 +11,10 @@ rebuilt, and of its albumentations stack only what its two training configs use 
     second generator seeded `seed + 1`) and carried behind the flag bytes (`hip.pack_image_aug`); `translate_pipeline`
     reads them off an albumentations-style Compose.  Sampling rules and attribute names restate albumentations 1.x, the
     kernel's 8-bit HSV conversions restate OpenCV's — from memory, neither is a dependency: parity with them is UNPINNED;
+    the geometry of the archived stacks and of the timm recipes rides in a second table of per-image records in the same
+    launch: PadIfNeeded's BORDER_REFLECT_101 (`pad_border`), MotionBlur (`motion_blur`) and RandomResizedCrop
+    (`random_resized_crop`, cut from a host canvas of `source_size` pixels), drawn by `draw_image_geom` from a fourth
+    generator seeded `seed + 3` (`hip.pack_image_geom`); applied as crop -> flips -> blur -> colour -> mix;
   * `ImbalancedDatasetSampler` (dataset.py:27-86: weights 1 / count[label], `torch.multinomial` with replacement) and
     `ShardedSampler` (one process per GPU: rank r takes indices r::W of a seed-shared permutation);
   * `get_dataset` honours `shuffle`, `weighted_sampling`, `drop_last`, `num_workers` (dataset.py:606-628).
@@ -51,11 +55,17 @@ class SyntheticDataset(Dataset):
 
 
 class FolderDataset(Dataset):
-    """raw=True: items are (uint8 HWC image resized so that its longest side is `size` and placed top-left in a
-    size x size canvas, (h, w), label) for DeviceLoader; raw=False: normalised float CHW, squashed to size x size."""
+    """raw=True: items are (uint8 HWC image resized so that its longest side is `source_size` and placed top-left in a
+    source_size x source_size canvas, (h, w), label) for DeviceLoader; raw=False: normalised float CHW, squashed to size x size.
+    source_size (default: size) is the host's LongestMaxSize target; a larger one than `size` gives the device's
+    RandomResizedCrop more pixels to cut from than it writes."""
 
-    def __init__(self, root, size=224, classes=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), raw=False):
+    def __init__(self, root, size=224, classes=None, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), raw=False,
+                 source_size=None):
         self.raw = raw
+        self.source_size = int(size if source_size is None else source_size)
+        if self.source_size != size and not raw:
+            raise ValueError("FolderDataset: source_size belongs to raw=True (the device pipeline)")
         root = Path(root)
         self.classes = classes or sorted(d.name for d in root.iterdir() if d.is_dir())
         self.items = [(p, i) for i, c in enumerate(self.classes) for p in sorted((root / c).iterdir())
@@ -72,10 +82,10 @@ class FolderDataset(Dataset):
         path, label = self.items[i]
         img = Image.open(path).convert("RGB")
         if self.raw:
-            # A.LongestMaxSize(size): scale so that max(h, w) == size (host side; decoding is here anyway)
-            k = self.size / max(img.size)
+            # A.LongestMaxSize(source_size): scale so that max(h, w) == source_size (host side; decoding is here anyway)
+            k = self.source_size / max(img.size)
             w, h = max(1, round(img.size[0] * k)), max(1, round(img.size[1] * k))
-            canvas = np.zeros((self.size, self.size, 3), np.uint8)
+            canvas = np.zeros((self.source_size, self.source_size, 3), np.uint8)
             canvas[:h, :w] = np.asarray(img.resize((w, h)), np.uint8)
             return torch.from_numpy(canvas), torch.tensor([h, w], dtype=torch.int32), label
         arr = np.asarray(img.resize((self.size, self.size)), np.float32).transpose(2, 0, 1) / 255.0
@@ -290,6 +300,187 @@ def draw_image_aug(gen, B, size, spec):
     return torch.from_numpy(bits), torch.from_numpy(rec)
 
 
+# ---- device-side geometry: RandomResizedCrop, MotionBlur and the reflect-101 pad border: the host draws ----------------------------------
+# The kernel applies what a per-image geometry record says (flag bit 4, include/nkbhip.h); this is where those records come from.
+# Argument names and sampling rules restate torchvision / albumentations 1.x from memory: parity with them is UNPINNED.
+GEOM_KEYS = ("random_resized_crop", "motion_blur")
+PAD_BORDERS = ("constant", "reflect_101")
+CROP_ATTEMPTS = 10
+_GEOM_DEFAULTS = {
+    "random_resized_crop": dict(scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), p=1.0),
+    "motion_blur": dict(blur_limit=7, allow_shifted=True, p=0.5),
+}
+
+
+def normalise_geom_spec(spec):
+    """{random_resized_crop, motion_blur: None or a dict of albumentations' argument names plus p; pad_border: None, "constant" or
+    "reflect_101"} -> the same with defaults filled in, blur_limit as a pair of odd kernel sizes (a scalar limit means (3, limit))
+    and pad_border always present; None when nothing is asked for (no transform, constant border).  Refuses what the kernel
+    cannot do: kernel sizes that are even, below 3 or above 15 (a record holds 16 taps), scale / ratio outside 0 < lo <= hi."""
+    spec = spec or {}
+    unknown = set(spec) - set(GEOM_KEYS) - {"pad_border"}
+    if unknown:
+        raise ValueError(f"unknown geometry keys {sorted(unknown)}; known: {GEOM_KEYS + ('pad_border',)}")
+    border = spec.get("pad_border") or "constant"
+    if border not in PAD_BORDERS:
+        raise ValueError(f"pad_border {border!r}; known: {PAD_BORDERS}")
+    out = {}
+    for key in GEOM_KEYS:
+        if spec.get(key) is None:
+            continue
+        extra = set(spec[key]) - set(_GEOM_DEFAULTS[key])
+        if extra:
+            raise ValueError(f"{key}: unknown arguments {sorted(extra)}; known: {sorted(_GEOM_DEFAULTS[key])}")
+        out[key] = {**_GEOM_DEFAULTS[key], **spec[key]}
+        if not 0.0 <= out[key]["p"] <= 1.0:
+            raise ValueError(f"{key}: p = {out[key]['p']!r} is no probability")
+    if not out and border == "constant":
+        return None
+    rrc, mb = (out.get(k) for k in GEOM_KEYS)
+    if rrc is not None:
+        for k in ("scale", "ratio"):
+            v = rrc[k]
+            if not isinstance(v, (tuple, list)) or len(v) != 2 or not 0 < v[0] <= v[1]:
+                raise ValueError(f"random_resized_crop: {k} must be a pair with 0 < lo <= hi, got {v!r}")
+            rrc[k] = (float(v[0]), float(v[1]))
+    if mb is not None:
+        lim = mb["blur_limit"]
+        lim = tuple(lim) if isinstance(lim, (tuple, list)) else (3, lim)
+        if len(lim) != 2 or any(int(k) != k or k % 2 == 0 or k < 3 or k > 15 for k in lim) or lim[0] > lim[1]:
+            raise ValueError(f"motion_blur: blur_limit needs odd kernel sizes in 3..15 with lo <= hi, got {mb['blur_limit']!r}")
+        mb["blur_limit"] = (int(lim[0]), int(lim[1]))
+        mb["allow_shifted"] = bool(mb["allow_shifted"])
+    out["pad_border"] = border
+    return out
+
+
+def geom_table_columns(spec):
+    """K of the per-batch torch.rand(B, K) table of draw_image_geom (spec: normalised)"""
+    return (1 + 4 * CROP_ATTEMPTS if "random_resized_crop" in spec else 0) + (8 if "motion_blur" in spec else 0)
+
+
+def line_taps(y1, x1, y2, x2):
+    """The 8-connected pixels of the line (x1, y1) -> (x2, y2) as [(y, x)]: one pixel per step along the longer axis,
+    max(|dx|, |dy|) + 1 in all; the other coordinate is k * d / L rounded half up over the first half of the steps and mirrored over
+    the second, so that a line whose ends are point-symmetric about a centre has point-symmetric pixels (Bresenham's pixels up to
+    the tie rule; cv2.line's own tie rule is not restated)."""
+    dy, dx = y2 - y1, x2 - x1
+    L = max(abs(dx), abs(dy))
+    if L == 0:
+        return [(y1, x1)]
+    along_x = abs(dx) >= abs(dy)
+    d_major, d_minor = (dx, dy) if along_x else (dy, dx)
+    D, s_major, s_minor = abs(d_minor), (1 if d_major > 0 else -1), (1 if d_minor > 0 else -1)
+    out = []
+    for k in range(L + 1):
+        kk = k if 2 * k <= L else L - k
+        m = (2 * kk * D + L) // (2 * L)
+        if 2 * k > L:
+            m = D - m
+        a, b = s_major * k, s_minor * m
+        out.append((y1 + b, x1 + a) if along_x else (y1 + a, x1 + b))
+    return out
+
+
+def _make_odd(v1, v2):
+    """albumentations' make_odd_val: an even number of pixels between v1 and v2 loses one at the larger end"""
+    if (abs(v1 - v2) + 1) % 2 != 1:
+        if v2 > v1:
+            v2 -= 1
+        else:
+            v1 -= 1
+    return v1, v2
+
+
+def draw_image_geom(gen, B, sizes, size, spec):
+    """The geometry draws of one batch -> (bits uint8 [B]: 16 where the image has a geometry record, records int32 [B, 16]).
+    sizes: None (every image is size x size) or [B, 2], the h and w of each image in its source slot; size: the output side.
+
+    ONE table u = torch.rand(B, K, generator=gen) per batch, K = geom_table_columns(spec), columns in this fixed order (a transform
+    that is None takes no columns; every column is drawn whether or not it is used):
+      random_resized_crop  [apply, then 10 x (area, log-ratio, row, col)], applied where apply < p.  torchvision's / albumentations'
+                           rule on the image's own h x w: area = U(scale) h w, aspect = exp(U(log r0, log r1)),
+                           bw = round(sqrt(area aspect)), bh = round(sqrt(area / aspect)); the first attempt with 0 < bw <= w and
+                           0 < bh <= h wins with y0 = randint(0, h - bh), x0 = randint(0, w - bw) from ITS row and col columns;
+                           after ten misses the central crop with the aspect clamped into `ratio`.  The record carries the box
+                           and the two scales float32(bh) / float32(size), float32(bw) / float32(size).
+      motion_blur          [apply, ksize, x1, x2, y1, y2, shift_x, shift_y], applied where apply < p.  Restated from albumentations
+                           1.x MotionBlur.get_params: ksize = a uniform choice among the odd sizes of blur_limit; the endpoints x1,
+                           x2 = randint(0, ksize - 1) each; y1 likewise; y2 likewise where x1 != x2, else one of the ksize - 1
+                           OTHER rows (random.sample of two rows), so the endpoints are distinct.  allow_shifted=False: both
+                           extents are made odd in length (make_odd_val) and the line is centred in the kernel.
+                           allow_shifted=True: the line is translated by shift_x = randint(-min(x1, x2), ksize - 1 - max(x1, x2))
+                           and shift_y alike, which keeps it inside the kernel — the explicit shift columns are this
+                           restatement's (1.x leaves the drawn endpoints where they are; both place the line uniformly).  The
+                           kernel's ones are line_taps(endpoints) in place of cv2.line; the record carries them as (dy, dx)
+                           offsets from the kernel centre ksize // 2, equal weights (kernel / kernel.sum()).
+    pad_border "reflect_101" sets mask bit 2 in every record and draws nothing.  U and randint as in draw_image_aug."""
+    from .hip import IMAGE_GEOM_BIT, IMAGE_GEOM_BLUR, IMAGE_GEOM_REFLECT, IMAGE_GEOM_WORDS, image_geom_record
+    spec = normalise_geom_spec(spec)
+    rec = np.zeros((B, IMAGE_GEOM_WORDS), np.int32)
+    if spec is None or B == 0:
+        return torch.zeros(B, dtype=torch.uint8), torch.from_numpy(rec)
+    K = geom_table_columns(spec)
+    u = torch.rand(B, K, generator=gen).double().numpy() if K else None
+    hw = np.full((B, 2), size, np.int64) if sizes is None else np.asarray(sizes).astype(np.int64).reshape(B, 2)
+    h, w = hw[:, 0], hw[:, 1]
+    col = 0
+    rrc, mb = (spec.get(k) for k in GEOM_KEYS)
+    if spec["pad_border"] == "reflect_101":
+        rec[:, 0] |= IMAGE_GEOM_REFLECT
+    if rrc is not None:
+        on = u[:, col] < rrc["p"]
+        logr = (np.log(rrc["ratio"][0]), np.log(rrc["ratio"][1]))
+        done = np.zeros(B, bool)
+        box = np.zeros((B, 4), np.int64)
+        for a in range(CROP_ATTEMPTS):
+            c = col + 1 + 4 * a
+            area = _uniform(rrc["scale"], u[:, c]) * h * w
+            aspect = np.exp(_uniform(logr, u[:, c + 1]))
+            bw = np.rint(np.sqrt(area * aspect)).astype(np.int64)
+            bh = np.rint(np.sqrt(area / aspect)).astype(np.int64)
+            ok = (bw > 0) & (bw <= w) & (bh > 0) & (bh <= h) & ~done
+            y0 = _randint(0, np.maximum(h - bh, 0), u[:, c + 2])
+            x0 = _randint(0, np.maximum(w - bw, 0), u[:, c + 3])
+            box[ok] = np.stack([y0, x0, bh, bw], 1)[ok]
+            done |= ok
+        in_ratio = w / h
+        fw = np.where(in_ratio > rrc["ratio"][1], np.rint(h * rrc["ratio"][1]), w).astype(np.int64)
+        fh = np.where(in_ratio < rrc["ratio"][0], np.rint(w / rrc["ratio"][0]), h).astype(np.int64)
+        fh, fw = np.clip(fh, 1, h), np.clip(fw, 1, w)
+        box[~done] = np.stack([(h - fh) // 2, (w - fw) // 2, fh, fw], 1)[~done]
+        rec[:, 0] |= on.astype(np.int32)
+        rec[:, 1:5] = np.where(on[:, None], box, 0)
+        f = rec.view(np.float32)
+        f[:, 5] = np.where(on, box[:, 2].astype(np.float32) / np.float32(size), np.float32(0))
+        f[:, 6] = np.where(on, box[:, 3].astype(np.float32) / np.float32(size), np.float32(0))
+        col += 1 + 4 * CROP_ATTEMPTS
+    if mb is not None:
+        lo, hi = mb["blur_limit"]
+        on = u[:, col] < mb["p"]
+        ks = lo + 2 * _randint(0, (hi - lo) // 2, u[:, col + 1])
+        for b in np.nonzero(on)[0]:
+            k = int(ks[b])
+            x1, x2, y1 = (int(_randint(0, k - 1, u[b, col + j])) for j in (2, 3, 4))
+            if x1 == x2:
+                y2 = int(_randint(0, k - 2, u[b, col + 5]))
+                y2 += y2 >= y1
+            else:
+                y2 = int(_randint(0, k - 1, u[b, col + 5]))
+            if mb["allow_shifted"]:
+                sx = int(_randint(-min(x1, x2), k - 1 - max(x1, x2), u[b, col + 6]))
+                sy = int(_randint(-min(y1, y2), k - 1 - max(y1, y2), u[b, col + 7]))
+            else:
+                (x1, x2), (y1, y2) = _make_odd(x1, x2), _make_odd(y1, y2)
+                sx, sy = k // 2 - (x1 + x2) // 2, k // 2 - (y1 + y2) // 2
+            taps = [(y - k // 2, x - k // 2) for y, x in line_taps(y1 + sy, x1 + sx, y2 + sy, x2 + sx)]
+            rec[b, 7:16] = image_geom_record(taps=taps)[7:16]
+            rec[b, 0] |= IMAGE_GEOM_BLUR
+        col += 8
+    bits = np.where(rec[:, 0] != 0, IMAGE_GEOM_BIT, 0).astype(np.uint8)
+    return torch.from_numpy(bits), torch.from_numpy(rec)
+
+
 MIX_MODES = ("batch", "pair", "elem")
 _MIX_DEFAULTS = dict(mixup_alpha=1.0, cutmix_alpha=0.0, cutmix_minmax=None, prob=1.0, switch_prob=0.5, mode="batch",
                      correct_lam=True)
@@ -367,16 +558,21 @@ def draw_batch_mix(rng, B, size, spec):
 
 
 # transforms of the reference stack, in the only order the kernel applies them
-_PIPELINE_ORDER = ("LongestMaxSize", "PadIfNeeded", "HorizontalFlip", "VerticalFlip", "RandomBrightnessContrast",
-                   "HueSaturationValue", "CoarseDropout", "Normalize", "ToTensorV2")
+_PIPELINE_ORDER = ("LongestMaxSize", "PadIfNeeded", "Resize", "RandomResizedCrop", "HorizontalFlip", "VerticalFlip", "MotionBlur",
+                   "RandomBrightnessContrast", "HueSaturationValue", "CoarseDropout", "Normalize", "ToTensorV2")
+_BORDER_MODES = {0: "constant", 4: "reflect_101"}          # cv2.BORDER_CONSTANT, cv2.BORDER_REFLECT_101
 
 
 def translate_pipeline(pipeline):
     """An albumentations-style Compose (anything with a `.transforms` list) -> the `data` keys of the device pipeline.
     Duck-typed on type(t).__name__ and on the attributes p, max_size, value, brightness_limit, contrast_limit,
-    hue_shift_limit, sat_shift_limit, val_shift_limit, min/max_holes, min/max_height, min/max_width, fill_value, mean, std
-    (restated from memory of albumentations 1.x: UNPINNED).  A transform outside the reference stack, or one out of the
-    stack's order, raises NotImplementedError."""
+    hue_shift_limit, sat_shift_limit, val_shift_limit, min/max_holes, min/max_height, min/max_width, fill_value, mean, std,
+    border_mode, height, width, size, scale, ratio, blur_limit, allow_shifted (restated from memory of albumentations 1.x:
+    UNPINNED).  A transform outside the reference stack, or one out of the stack's order, raises NotImplementedError; so does a
+    PadIfNeeded border other than constant (0) or reflect-101 (4) and a Resize to anything but the stack's own square size (the
+    reference's archived stacks resize the padded square to its own size: a no-op).  A PadIfNeeded without a border_mode
+    attribute keeps the constant border.  RandomResizedCrop to a size other than LongestMaxSize's makes that one the
+    `source_size` of the host and its own the output `size`."""
     out, last = {}, -1
     for t in pipeline.transforms:
         name = type(t).__name__
@@ -394,6 +590,27 @@ def translate_pipeline(pipeline):
         elif name == "PadIfNeeded":
             if getattr(t, "value", None) is not None:
                 out["fill"] = float(t.value)
+            mode = getattr(t, "border_mode", None)
+            if mode is not None:
+                if mode not in _BORDER_MODES:
+                    raise NotImplementedError(f"device pipeline: PadIfNeeded border_mode {mode!r} is not built (0 = constant and "
+                                              f"4 = reflect-101 are)")
+                out["pad_border"] = _BORDER_MODES[mode]
+        elif name == "Resize":
+            if "size" not in out or not (int(t.height) == int(t.width) == out["size"]):
+                raise NotImplementedError(f"device pipeline: Resize to {t.height} x {t.width} is not built: only the no-op onto the "
+                                          f"stack's own {out.get('size', '(unset)')}-pixel square is accepted")
+        elif name == "RandomResizedCrop":
+            side = getattr(t, "size", None)
+            hh, ww = (side if isinstance(side, (tuple, list)) else (side, side)) if side is not None else (t.height, t.width)
+            if int(hh) != int(ww):
+                raise NotImplementedError(f"device pipeline: RandomResizedCrop to {hh} x {ww} is not built (square outputs only)")
+            if "size" in out and out["size"] != int(hh):
+                out["source_size"] = out["size"]
+            out["size"] = int(hh)
+            out["random_resized_crop"] = dict(scale=tuple(t.scale), ratio=tuple(t.ratio), p=p)
+        elif name == "MotionBlur":
+            out["motion_blur"] = dict(blur_limit=t.blur_limit, allow_shifted=getattr(t, "allow_shifted", True), p=p)
         elif name == "HorizontalFlip":
             out["hflip_p"] = p
         elif name == "VerticalFlip":
@@ -429,11 +646,17 @@ class DeviceLoader:
     THIRD generator, numpy's default_rng(seed + 2); the mixing instructions ride in words 10..15 of the records, the image is
     mixed inside the prep launch, and the target of a batch with a mixed image becomes a losses.MixedTarget (a dict of them
     for dict targets: one lam and one partner shared by all tasks) uploaded with the batch.  A batch without a mixed image keeps
-    its plain labels.  With mixup None nothing changes: same draws, same buffers."""
+    its plain labels.  With mixup None nothing changes: same draws, same buffers.
+
+    random_resized_crop / motion_blur: None or a dict of albumentations' argument names plus `p`; pad_border: None, "constant" or
+    "reflect_101" (normalise_geom_spec).  Their draws (draw_image_geom) come from a FOURTH generator seeded `seed + 3`; the
+    geometry records ride in a second table behind the first (hip.pack_image_geom) and are applied in the same launch, in front
+    of the flips: crop -> flips -> blur -> colour -> mix.  A batch whose source canvas is larger than `size` needs
+    random_resized_crop with p == 1.  With all three None nothing changes: same draws, same buffers, same launch arguments."""
 
     def __init__(self, loader, device, size, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), hflip_p=0.0,
                  vflip_p=0.0, fill=0.0, seed=0, brightness_contrast=None, hue_saturation_value=None, coarse_dropout=None,
-                 mixup=None):
+                 mixup=None, random_resized_crop=None, motion_blur=None, pad_border=None):
         self.loader, self.device = loader, torch.device(device)
         self.size, self.mean, self.std, self.fill = size, tuple(mean), tuple(std), float(fill)
         self.hflip_p, self.vflip_p = float(hflip_p), float(vflip_p)
@@ -443,19 +666,22 @@ class DeviceLoader:
         self.aug_gen = torch.Generator().manual_seed(seed + 1)
         self.mixup = normalise_mix_spec(mixup)
         self.mix_rng = np.random.default_rng(seed + 2)
+        self.geom = normalise_geom_spec(dict(random_resized_crop=random_resized_crop, motion_blur=motion_blur, pad_border=pad_border))
+        self.geom_gen = torch.Generator().manual_seed(seed + 3)
         self.dataset = getattr(loader, "dataset", None)
         self._copy = None
 
     def __len__(self):
         return len(self.loader)
 
-    def draw_flags(self, B):
+    def draw_flags(self, B, sizes=None):
         """The host draws of one batch -> what nkb_image_prep takes as `flags`: None, uint8 [B] flip bits (one torch.rand(B, 2)
         from the flip generator), or, with augmentations or mixup on, those bits | the record bits with the record table behind
-        them."""
-        return self._draw(B)[0]
+        them; with a geometry transform on, the geometry bits and table as well (sizes: the batch's [B, 2] h and w, None =
+        every image fills the size x size canvas)."""
+        return self._draw(B, sizes)[0]
 
-    def _draw(self, B):
+    def _draw(self, B, sizes=None):
         """(flags as draw_flags returns them, None or the (partner int64 [B], lam float64 [B]) of a batch with a mixed image)"""
         flags = None
         if self.hflip_p > 0 or self.vflip_p > 0:
@@ -473,7 +699,14 @@ class DeviceLoader:
             bits = bits | mbits
             if bool(mbits.any()):
                 mix = (partner, lam)
-        if records is not None:
+        if self.geom is not None:
+            from . import hip
+            gbits, grec = draw_image_geom(self.geom_gen, B, sizes, self.size, self.geom)
+            for other in (flags, bits):
+                if other is not None:
+                    gbits = gbits | other
+            flags = hip.pack_image_geom(gbits, records, grec, sizes=sizes)
+        elif records is not None:
             from . import hip
             flags = hip.pack_image_aug(bits if flags is None else flags | bits, records)
         return flags, mix
@@ -494,7 +727,14 @@ class DeviceLoader:
             (raw, target), sizes = item, None
         if raw.dtype != torch.uint8 or raw.dim() != 4 or raw.shape[-1] != 3:
             raise RuntimeError(f"DeviceLoader expects uint8 [B,H,W,3] batches, got {tuple(raw.shape)} {raw.dtype}")
-        flags, mix = self._draw(raw.shape[0])
+        B, Hs, Ws = raw.shape[:3]
+        if max(Hs, Ws) > self.size and not (self.geom is not None and self.geom.get("random_resized_crop", {}).get("p") == 1.0):
+            raise ValueError(f"DeviceLoader: a {Hs} x {Ws} source canvas is larger than the {self.size}-pixel output; that needs "
+                             f"random_resized_crop with p = 1, so that every image is resampled")
+        own = sizes
+        if self.geom is not None and own is None:
+            own = torch.tensor([[Hs, Ws]], dtype=torch.int32).expand(B, 2)
+        flags, mix = self._draw(B, own)
         if mix is not None:
             if isinstance(target, dict):
                 target = {k: self._mixed_target(v, mix).pin_memory() for k, v in target.items()}
@@ -556,7 +796,10 @@ def get_dataset(data, pipeline=None):
     training.  `mixup` (None or a dict of timm.data.Mixup's argument names: mixup_alpha, cutmix_alpha, prob, switch_prob, mode) mixes
     the batch inside the device pipeline and needs `device_pipeline`.  With `device_pipeline` the keys `brightness_contrast`, `hue_saturation_value`, `coarse_dropout` (None or a dict of
     albumentations' argument names plus `p`) and `fill` go to the DeviceLoader too, and a `pipeline` that has a `.transforms`
-    list is translated into all of these keys (translate_pipeline); explicit `data` keys win over the translated ones."""
+    list is translated into all of these keys (translate_pipeline); explicit `data` keys win over the translated ones.
+    `random_resized_crop`, `motion_blur` (None or a dict of albumentations' argument names plus `p`) and `pad_border` ("constant" or
+    "reflect_101") are the device pipeline's geometry; `source_size` (default `size`) is the host's LongestMaxSize target and canvas
+    side, and a larger one than `size` needs random_resized_crop with p == 1."""
     kind = data.get("type", "folder")
     on_device = bool(data.get("device_pipeline", False))
     if on_device and isinstance(getattr(pipeline, "transforms", None), (list, tuple)):
@@ -564,11 +807,24 @@ def get_dataset(data, pipeline=None):
     size = data.get("size", 224)
     if data.get("mixup") is not None and not (on_device and kind != "synthetic"):
         raise NotImplementedError("mixup is built into the device pipeline only: set device_pipeline=True on a folder dataset")
+    geom = normalise_geom_spec({k: data.get(k) for k in GEOM_KEYS + ("pad_border",)})
+    if geom is not None and not (on_device and kind != "synthetic"):
+        raise NotImplementedError("random_resized_crop, motion_blur and pad_border are built into the device pipeline only: set "
+                                  "device_pipeline=True on a folder dataset")
+    source_size = int(data.get("source_size", size))
+    if source_size != size and not on_device:
+        raise ValueError("source_size belongs to the device pipeline (device_pipeline=True)")
+    if source_size < size:
+        raise ValueError(f"source_size = {source_size} is smaller than size = {size}: the host would upscale what the device crops")
+    if source_size > size and not (geom is not None and geom.get("random_resized_crop", {}).get("p") == 1.0):
+        raise ValueError(f"source_size = {source_size} > size = {size} needs random_resized_crop with p = 1, so that every image is "
+                         f"resampled onto the output; anything else has no {size}-pixel image to show")
     if kind == "synthetic":
         ds = SyntheticDataset(data["n_images"], data["classes"], size=size, seed=data.get("seed", 1234))
         on_device = False
     elif "root" in data:
-        ds = FolderDataset(data["root"], size=size, classes=data.get("classes"), raw=on_device)
+        ds = FolderDataset(data["root"], size=size, classes=data.get("classes"), raw=on_device,
+                           source_size=source_size if on_device else None)
     else:
         raise NotImplementedError(
             f"dataset type {kind!r}: the reference's annotation / augmentation datasets (dataset.py:183-538) are "
@@ -587,5 +843,6 @@ def get_dataset(data, pipeline=None):
         return DeviceLoader(loader, data.get("device", "cuda:0"), size, mean=data.get("mean", (0.485, 0.456, 0.406)),
                             std=data.get("std", (0.229, 0.224, 0.225)), hflip_p=data.get("hflip_p", 0.0),
                             vflip_p=data.get("vflip_p", 0.0), fill=data.get("fill", 0.0), seed=data.get("seed", 0),
-                            **{k: data.get(k) for k in AUG_KEYS}, mixup=data.get("mixup"))
+                            **{k: data.get(k) for k in AUG_KEYS}, mixup=data.get("mixup"),
+                            **{k: data.get(k) for k in GEOM_KEYS + ("pad_border",)})
     return loader

@@ -986,11 +986,92 @@ def pack_image_aug(flags, records):
     return buf
 
 
+IMAGE_GEOM_BIT, IMAGE_GEOM_WORDS, IMAGE_GEOM_MAX_TAPS = 16, 16, 16    # flag bit 4, words per geometry record, blur taps per record (nkbhip.h)
+IMAGE_GEOM_RESAMPLE, IMAGE_GEOM_BLUR, IMAGE_GEOM_REFLECT = 1, 2, 4    # word 0 of a geometry record
+
+
+def image_geom_bytes(B):
+    """length of a flags buffer that carries geometry records: image_aug_bytes(B), then 64 bytes per image"""
+    return image_aug_bytes(B) + 4 * IMAGE_GEOM_WORDS * B
+
+
+def image_geom_record(box=None, out_size=None, taps=None, reflect=False):
+    """One geometry record, int32 numpy [16].  box: (y0, x0, bh, bw) in the image's source coordinates, resampled onto out_size =
+    (Ho, Wo) — the two scales are divided here, in float32; taps: [(dy, dx), ..], 1..16 of them within +-127; reflect: the pad stage
+    reflects (BORDER_REFLECT_101) instead of filling."""
+    import numpy as np
+    g = np.zeros(IMAGE_GEOM_WORDS, np.int32)
+    if box is not None:
+        y0, x0, bh, bw = (int(v) for v in box)
+        if y0 < 0 or x0 < 0 or bh < 1 or bw < 1:
+            raise ValueError(f"image_geom_record: box {tuple(box)} needs y0, x0 >= 0 and bh, bw >= 1")
+        g[0] |= IMAGE_GEOM_RESAMPLE
+        g[1:5] = (y0, x0, bh, bw)
+        f = g.view(np.float32)
+        f[5] = np.float32(bh) / np.float32(out_size[0])
+        f[6] = np.float32(bw) / np.float32(out_size[1])
+    if taps is not None:
+        if not 1 <= len(taps) <= IMAGE_GEOM_MAX_TAPS:
+            raise ValueError(f"image_geom_record: {len(taps)} taps; a record holds 1..{IMAGE_GEOM_MAX_TAPS}")
+        g[0] |= IMAGE_GEOM_BLUR
+        g[7] = len(taps)
+        words = np.zeros(8, np.uint32)
+        for t, (dy, dx) in enumerate(taps):
+            if not (-127 <= int(dy) <= 127 and -127 <= int(dx) <= 127):
+                raise ValueError(f"image_geom_record: tap ({dy}, {dx}) lies outside +-127")
+            words[t // 2] |= np.uint32(((int(dy) & 0xFF) | ((int(dx) & 0xFF) << 8)) << (16 * (t % 2)))
+        g[8:16] = words.view(np.int32)
+    if reflect:
+        g[0] |= IMAGE_GEOM_REFLECT
+    return g
+
+
+def pack_image_geom(flags, records, geom, sizes=None):
+    """flags uint8 [B] (bit 4 = IMAGE_GEOM_BIT: this image has a geometry record), records int32 [B, 64] or None (no augmentation
+    or mixing record anywhere: the table is zero-filled), geom int32 [B, 16] (host tensors) -> the uint8 buffer nkb_image_prep reads
+    when a bit 4 is set: the layout of pack_image_aug, then the geometry table.  Of the images with bit 4 it refuses a crop box that
+    is empty, negative or — where sizes (int32 [B, 2], h and w per image) are given — outside the image, a tap count outside
+    1..16 and a tap offset of -128."""
+    B = flags.numel()
+    if geom.dtype != torch.int32 or tuple(geom.shape) != (B, IMAGE_GEOM_WORDS) or geom.is_cuda:
+        raise RuntimeError(f"pack_image_geom: expected host int32 [B, {IMAGE_GEOM_WORDS}] geometry records, got "
+                           f"{tuple(geom.shape)} {geom.dtype}")
+    if records is None:
+        records = torch.zeros(B, IMAGE_AUG_WORDS, dtype=torch.int32)
+    head = pack_image_aug(flags, records)
+    on = (flags.reshape(-1) & IMAGE_GEOM_BIT) != 0
+    crop = on & ((geom[:, 0] & IMAGE_GEOM_RESAMPLE) != 0)
+    if bool(crop.any()):
+        y0, x0, bh, bw = (geom[crop, j].long() for j in range(1, 5))
+        if bool(((y0 < 0) | (x0 < 0) | (bh < 1) | (bw < 1)).any()):
+            raise RuntimeError("pack_image_geom: a crop box (words 1..4) is empty or starts below 0")
+        if sizes is not None:
+            hw = sizes.reshape(B, 2)[crop].long()
+            if bool(((y0 + bh > hw[:, 0]) | (x0 + bw > hw[:, 1])).any()):
+                raise RuntimeError("pack_image_geom: a crop box (words 1..4) reaches outside its image's h x w")
+    blur = on & ((geom[:, 0] & IMAGE_GEOM_BLUR) != 0)
+    if bool(blur.any()):
+        n = geom[blur, 7]
+        if bool(((n < 1) | (n > IMAGE_GEOM_MAX_TAPS)).any()):
+            raise RuntimeError(f"pack_image_geom: a tap count (word 7) lies outside 1..{IMAGE_GEOM_MAX_TAPS}")
+        offs = geom[blur, 8:16].contiguous().view(torch.int8).reshape(-1, 2 * IMAGE_GEOM_MAX_TAPS)
+        used = torch.arange(2 * IMAGE_GEOM_MAX_TAPS)[None, :] < 2 * n.long()[:, None]
+        if bool(((offs == -128) & used).any()):
+            raise RuntimeError("pack_image_geom: a tap offset lies outside +-127")
+    buf = torch.zeros(image_geom_bytes(B), dtype=torch.uint8, pin_memory=head.is_pinned() and geom.is_pinned())
+    buf[:head.numel()] = head
+    buf[head.numel():] = geom.contiguous().view(torch.uint8).reshape(-1)
+    return buf
+
+
 def image_prep(src, sizes, flags, out, B, Hs, Ws, Ho, Wo, mean, std, fill=0.0):
-    """flags: None, uint8 [B], or the buffer of pack_image_aug (the C side cannot see device bits: the layout is kept here)"""
-    if flags is not None and flags.numel() > B and (flags.numel() != image_aug_bytes(B) or flags.data_ptr() % 16):
+    """flags: None, uint8 [B], or the buffer of pack_image_aug / pack_image_geom (the C side cannot see device bits: the layout is
+    kept here)"""
+    if flags is not None and flags.numel() > B and (flags.numel() not in (image_aug_bytes(B), image_geom_bytes(B))
+                                                    or flags.data_ptr() % 16):
         raise RuntimeError(f"image_prep: a flags buffer longer than B = {B} must be the 16-byte aligned {image_aug_bytes(B)}-byte "
-                           f"layout of pack_image_aug, got {flags.numel()} bytes at offset {flags.data_ptr() % 16}")
+                           f"layout of pack_image_aug or the {image_geom_bytes(B)}-byte one of pack_image_geom, got "
+                           f"{flags.numel()} bytes at offset {flags.data_ptr() % 16}")
     m, sd = (C.c_float * 3)(*mean), (C.c_float * 3)(*std)
     check(load().nkb_image_prep(ptr(src), ptr(sizes), ptr(flags), ptr(out), B, Hs, Ws, Ho, Wo, C.cast(m, C.c_void_p),
                                 C.cast(sd, C.c_void_p), float(fill), stream()), "image_prep")
