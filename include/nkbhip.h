@@ -645,7 +645,32 @@ int nkb_loss_backward(const float* probs, int ldp, const long long* target, cons
  * (both may be NULL): callers from before the momentum form hand kind 3 Adam's betas with zeros in c0..c3, and keep their
  * result. Kinds 0..2 need both m and v: a NULL one is refused.
  * skip_flag (device float, may be NULL): the launch does nothing when *skip_flag != 0 — the skipped step of
- * GradScaler.step (engine.py:59) decided on the device. */
+ * GradScaler.step (engine.py:59) decided on the device.
+ *
+ * Gradient clipping: kind | NKB_OPTIM_CLIP_NORM or kind | NKB_OPTIM_CLIP_VALUE with kind in 0..3 (both bits at once, and any other
+ * bit, are refused).  skip_flag then points at a read-only device record of floats, which the kernel never writes (a NULL
+ * record is refused):
+ *     rec[0]         the skip flag, as above          rec[1]  max_norm (norm form) / the clamp value (value form)
+ *     rec[2]         P, the number of partial sums, as a float, 1 <= P <= 4096 (the kernel reads min(P, 4096))
+ *     rec[3]         reserved, 0                      rec[4 .. 4 + P)  partial sums of squares of the raw gradient (norm form only)
+ *   Norm form (torch.nn.utils.clip_grad_norm_): every workgroup of 256 threads rebuilds the coefficient from the partials in one
+ *   fixed order: thread t adds partials t, t + 256, .. in rising order, then the wave's xor butterfly (offsets 32, 16, .. 1),
+ *   then the four wave sums in wave order; norm = sqrtf(total) * fabsf(grad_scale); coef = rec[1] / (norm + 1e-6f), replaced by 1
+ *   only when coef >= 1.f (a NaN coef stays NaN, as torch.clamp(max=1) keeps it).  The element update uses
+ *   grad = (g * grad_scale) * coef, two multiplications with one rounding each (the data-parallel average first, the clip second)
+ *   and is otherwise the unclipped one.  The coefficient has the same bits in every workgroup and in every launch of a step that
+ *   share a record, and nothing is accumulated with atomics: a clipped step is bit-reproducible like a plain one.
+ *   The partials come from nkb_segment_sumsq over the gradient arena cut into P chunks, out = rec + 4.
+ *   Value form (clip_grad_value_): grad = g * grad_scale clamped to [-rec[1], rec[1]]; a NaN stays NaN; rec[2..] is not read.
+ *
+ * Weight EMA: kind == NKB_OPTIM_EMA exactly (32 with any other bit is refused).  p is the EMA range (read and written), g the
+ * model's fp32 master weights (read); m and v are ignored and may be NULL; beta1 = d and beta2 = 1 - d (subtracted in double
+ * on the host, rounded once); e = (beta1 * e) + (beta2 * w): two products and a sum, three roundings, never an fma.
+ * shadow_bf16 (optional) receives the bf16 of the new EMA values.  Every other float argument is ignored; skip_flag may be NULL
+ * and is otherwise the plain one-float flag.  n == 0 returns 0 without a launch.  12 bytes per parameter, 14 with the shadow. */
+#define NKB_OPTIM_CLIP_NORM  16   /* kind | 16: scale the gradient by a coefficient the kernel derives from a device record */
+#define NKB_OPTIM_CLIP_VALUE 64   /* kind | 64: clamp the gradient to [-rec[1], rec[1]] */
+#define NKB_OPTIM_EMA        32   /* kind == 32 exactly: p = d * p + (1 - d) * g, no optimizer math */
 int nkb_optim_step(int kind, float* p, const float* g, float* m, float* v, void* shadow_bf16, long long n, float lr,
                    float wd, float beta1, float beta2, float eps, float grad_scale, float c0, float c1, float c2,
                    float c3, const float* skip_flag, nkb_stream_t stream);

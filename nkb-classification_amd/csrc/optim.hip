@@ -3,6 +3,8 @@
 // instantiated by the reference (/root/reference/nkb_classification/utils.py:29-42) and by utils.get_optimizer's optional keys.
 // Step-dependent scalars are computed on the host in double precision and passed in; element math is fp32 in torch's
 // operation order.  Optionally emits the bf16 shadow copy of the updated parameters in the same pass.
+// Flag bits on `kind` (nkbhip.h) clip the gradient inside the launch, by a coefficient every workgroup derives from a device record
+// (norm form) or by a clamp (value form); kind NKB_OPTIM_EMA turns the launch into the weight-EMA pass over the same arena.
 #include "common.h"
 
 struct OptimArgs {
@@ -26,10 +28,36 @@ __host__ __device__ __forceinline__ int optim_mode(int kind, float beta1, float 
     return kind != 3 ? OPTIM_ADAM_FAMILY : (beta1 != 0.f && c0 != 0.f ? OPTIM_SGD_MOMENTUM : OPTIM_SGD_PLAIN);
 }
 
+// Gradient clipping rides on the launch (kind | NKB_OPTIM_CLIP_NORM / NKB_OPTIM_CLIP_VALUE, record layout in nkbhip.h): like the
+// three modes it is uniform per launch, so each form is an instantiation of its own and the plain one (CLIP_NONE) is the code
+// from before the clip forms.  `clip` is the coefficient of the norm form, the bound of the value form.
+enum { CLIP_NONE = 0, CLIP_NORM = 1, CLIP_VALUE = 2 };
+constexpr int OPTIM_MAX_PARTIALS = 4096;
+
+// The norm form's coefficient, rebuilt by every workgroup (256 threads) from the record's partial sums of squares in one fixed
+// order, so that it has the same bits in every workgroup and every launch of a step: thread t adds partials t, t + 256, .. in
+// rising order, the wave's xor butterfly follows, then the four wave sums in wave order.  No atomics, nothing written.
+__device__ __forceinline__ float clip_norm_coef(const float* __restrict__ rec, float grad_scale) {
+    __shared__ float s[4];
+    const float pf = rec[2];
+    const int P = pf >= (float)OPTIM_MAX_PARTIALS ? OPTIM_MAX_PARTIALS : (pf >= 1.f ? (int)pf : 0);
+    float t = 0.f;
+    for (int i = threadIdx.x; i < P; i += 256) t += rec[4 + i];
+    t = wave_sum(t);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = t;
+    __syncthreads();
+    const float total = s[0] + s[1] + s[2] + s[3];
+    const float norm = sqrtf(total) * fabsf(grad_scale);
+    const float coef = rec[1] / (norm + 1e-6f);        // torch.nn.utils.clip_grad_norm_: max_norm / (total_norm + 1e-6)
+    return coef >= 1.f ? 1.f : coef;                    // clamp(max=1): a NaN stays a NaN
+}
+
 // one element of the update (the arithmetic of torch's single-tensor Adam / NAdam / RAdam / SGD loops, op for op)
-template <int MODE>
-__device__ __forceinline__ void optim_one(float& w, float grad, float& mi, float& vi, const OptimArgs& a) {
-    grad = grad * a.grad_scale;
+template <int MODE, int CLIP>
+__device__ __forceinline__ void optim_one(float& w, float grad, float& mi, float& vi, const OptimArgs& a, float clip) {
+    grad = grad * a.grad_scale;                              // the data-parallel average first, the clip second (torch's order)
+    if (CLIP == CLIP_NORM) grad = grad * clip;
+    if (CLIP == CLIP_VALUE) grad = grad > clip ? clip : (grad < -clip ? -clip : grad);   // torch.clamp: a NaN stays a NaN
     if (MODE != OPTIM_ADAM_FAMILY) {                         // SGD
         grad = grad + a.wd * w;
         if (MODE == OPTIM_SGD_MOMENTUM) {
@@ -62,9 +90,10 @@ __device__ __forceinline__ void optim_one(float& w, float grad, float& mi, float
 // parameters per lane per access (16-byte loads / stores on every stream) and two such groups in flight per thread: 5.3 TB/s
 // standalone (scripts/optim_bench.py: 304 M parameters in 1.73 ms); unicom ViT-L/14's 573 M parameters take 3.13 ms in the step
 // (5.5 TB/s) against 3.6 ms for the one-element-per-thread form this replaces.
-template <int MODE>
+template <int MODE, int CLIP>
 __device__ __forceinline__ void optim_step_vec(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                               float* __restrict__ v, bf16_t* __restrict__ shadow, size_t n, const OptimArgs& a) {
+                                               float* __restrict__ v, bf16_t* __restrict__ shadow, size_t n, const OptimArgs& a,
+                                               float clip) {
     constexpr bool use_m = MODE != OPTIM_SGD_PLAIN, use_v = MODE == OPTIM_ADAM_FAMILY;
     const size_t n4 = n >> 2, stride = (size_t)gridDim.x * blockDim.x;
     f32x4* p4 = (f32x4*)p; const f32x4* g4 = (const f32x4*)g; f32x4* m4 = (f32x4*)m; f32x4* v4 = (f32x4*)v;
@@ -88,7 +117,7 @@ __device__ __forceinline__ void optim_step_vec(float* __restrict__ p, const floa
             if (u == 1 && !two) break;
             const size_t i = u ? i1 : i0;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { float w_ = w[u][e], m_ = mi[u][e], v_ = vi[u][e]; optim_one<MODE>(w_, gr[u][e], m_, v_, a); w[u][e] = w_; mi[u][e] = m_; vi[u][e] = v_; }
+            for (int e = 0; e < 4; ++e) { float w_ = w[u][e], m_ = mi[u][e], v_ = vi[u][e]; optim_one<MODE, CLIP>(w_, gr[u][e], m_, v_, a, clip); w[u][e] = w_; mi[u][e] = m_; vi[u][e] = v_; }
             if (use_m) __builtin_nontemporal_store(mi[u], m4 + i);
             if (use_v) __builtin_nontemporal_store(vi[u], v4 + i);
             __builtin_nontemporal_store(w[u], p4 + i);
@@ -103,51 +132,145 @@ __device__ __forceinline__ void optim_step_vec(float* __restrict__ p, const floa
     // (n % 4 tail)
     for (size_t i = (n4 << 2) + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         float w_ = p[i], m_ = use_m ? m[i] : 0.f, v_ = use_v ? v[i] : 0.f;
-        optim_one<MODE>(w_, g[i], m_, v_, a);
+        optim_one<MODE, CLIP>(w_, g[i], m_, v_, a, clip);
         if (use_m) m[i] = m_;
         if (use_v) v[i] = v_;
         p[i] = w_;
         if (shadow) shadow[i] = f2bf(w_);
     }
 }
+// skip: one device float, or with a clip form the record {skip, bound, P, 0, partials[P]} (never written)
+template <int CLIP>
 __global__ void __launch_bounds__(256) optim_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                          float* __restrict__ v, bf16_t* __restrict__ shadow, size_t n,
                                                          const OptimArgs a, const float* __restrict__ skip) {
     // skipped step of the gradient scaler (engine.py:59, GradScaler.step): decided on the device, no host round trip
     if (skip && *skip != 0.f) return;
+    const float clip = CLIP == CLIP_NORM ? clip_norm_coef(skip, a.grad_scale) : (CLIP == CLIP_VALUE ? skip[1] : 0.f);
     const int mode = optim_mode(a.kind, a.beta1, a.c0);
-    if (mode == OPTIM_ADAM_FAMILY) optim_step_vec<OPTIM_ADAM_FAMILY>(p, g, m, v, shadow, n, a);
-    else if (mode == OPTIM_SGD_PLAIN) optim_step_vec<OPTIM_SGD_PLAIN>(p, g, m, v, shadow, n, a);
-    else optim_step_vec<OPTIM_SGD_MOMENTUM>(p, g, m, v, shadow, n, a);
+    if (mode == OPTIM_ADAM_FAMILY) optim_step_vec<OPTIM_ADAM_FAMILY, CLIP>(p, g, m, v, shadow, n, a, clip);
+    else if (mode == OPTIM_SGD_PLAIN) optim_step_vec<OPTIM_SGD_PLAIN, CLIP>(p, g, m, v, shadow, n, a, clip);
+    else optim_step_vec<OPTIM_SGD_MOMENTUM, CLIP>(p, g, m, v, shadow, n, a, clip);
 }
 // the same, one parameter per thread: ranges that do not start on a 16-byte boundary
-template <int MODE>
+template <int MODE, int CLIP>
 __device__ __forceinline__ void optim_step_scalar(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                  float* __restrict__ v, bf16_t* __restrict__ shadow, size_t n, const OptimArgs& a) {
+                                                  float* __restrict__ v, bf16_t* __restrict__ shadow, size_t n, const OptimArgs& a,
+                                                  float clip) {
     constexpr bool use_m = MODE != OPTIM_SGD_PLAIN, use_v = MODE == OPTIM_ADAM_FAMILY;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
         float w_ = p[i], m_ = use_m ? m[i] : 0.f, v_ = use_v ? v[i] : 0.f;
-        optim_one<MODE>(w_, g[i], m_, v_, a);
+        optim_one<MODE, CLIP>(w_, g[i], m_, v_, a, clip);
         if (use_m) m[i] = m_;
         if (use_v) v[i] = v_;
         p[i] = w_;
         if (shadow) shadow[i] = f2bf(w_);
     }
 }
-__global__ void optim_step_scalar_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                         float* __restrict__ v, bf16_t* __restrict__ shadow, size_t n, const OptimArgs a,
-                                         const float* __restrict__ skip) {
+template <int CLIP>
+__global__ void __launch_bounds__(256) optim_step_scalar_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                                float* __restrict__ m, float* __restrict__ v,
+                                                                bf16_t* __restrict__ shadow, size_t n, const OptimArgs a,
+                                                                const float* __restrict__ skip) {
     if (skip && *skip != 0.f) return;
+    const float clip = CLIP == CLIP_NORM ? clip_norm_coef(skip, a.grad_scale) : (CLIP == CLIP_VALUE ? skip[1] : 0.f);
     const int mode = optim_mode(a.kind, a.beta1, a.c0);
-    if (mode == OPTIM_ADAM_FAMILY) optim_step_scalar<OPTIM_ADAM_FAMILY>(p, g, m, v, shadow, n, a);
-    else if (mode == OPTIM_SGD_PLAIN) optim_step_scalar<OPTIM_SGD_PLAIN>(p, g, m, v, shadow, n, a);
-    else optim_step_scalar<OPTIM_SGD_MOMENTUM>(p, g, m, v, shadow, n, a);
+    if (mode == OPTIM_ADAM_FAMILY) optim_step_scalar<OPTIM_ADAM_FAMILY, CLIP>(p, g, m, v, shadow, n, a, clip);
+    else if (mode == OPTIM_SGD_PLAIN) optim_step_scalar<OPTIM_SGD_PLAIN, CLIP>(p, g, m, v, shadow, n, a, clip);
+    else optim_step_scalar<OPTIM_SGD_MOMENTUM, CLIP>(p, g, m, v, shadow, n, a, clip);
+}
+
+// ---- weight EMA (kind == NKB_OPTIM_EMA): e = (d * e) + (omd * w) over the arena, ModelEmaV2's decay * e + (1 - decay) * m -------
+// Two products and one sum, three roundings: this file is compiled with -ffp-contract=off (csrc/Makefile), so nothing becomes an
+// fma.  12 bytes per parameter (EMA read + written, master weight read), 14 with the bf16 shadow of the new values; accesses, the
+// two groups in flight and the grid are those of optim_step_vec.
+__device__ __forceinline__ float ema_one(float e, float w, float d, float omd) { return (d * e) + (omd * w); }
+__global__ void __launch_bounds__(256) ema_step_kernel(float* __restrict__ e, const float* __restrict__ w,
+                                                       bf16_t* __restrict__ shadow, size_t n, float d, float omd,
+                                                       const float* __restrict__ skip) {
+    if (skip && *skip != 0.f) return;
+    const size_t n4 = n >> 2, stride = (size_t)gridDim.x * blockDim.x;
+    f32x4* e4 = (f32x4*)e; const f32x4* w4 = (const f32x4*)w;
+    u32x2* s2 = (u32x2*)shadow;
+    for (size_t i0 = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i0 < n4; i0 += 2 * stride) {
+        const size_t i1 = i0 + stride;
+        const bool two = i1 < n4;
+        f32x4 ev[2], wv[2];
+        ev[0] = e4[i0]; wv[0] = __builtin_nontemporal_load(w4 + i0);
+        if (two) { ev[1] = e4[i1]; wv[1] = __builtin_nontemporal_load(w4 + i1); }
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (u == 1 && !two) break;
+            const size_t i = u ? i1 : i0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ev[u][k] = ema_one(ev[u][k], wv[u][k], d, omd);
+            __builtin_nontemporal_store(ev[u], e4 + i);
+            if (shadow) {
+                u32x2 o;
+                o[0] = (unsigned)f2bf(ev[u][0]) | ((unsigned)f2bf(ev[u][1]) << 16);
+                o[1] = (unsigned)f2bf(ev[u][2]) | ((unsigned)f2bf(ev[u][3]) << 16);
+                s2[i] = o;
+            }
+        }
+    }
+    for (size_t i = (n4 << 2) + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float r = ema_one(e[i], w[i], d, omd);
+        e[i] = r;
+        if (shadow) shadow[i] = f2bf(r);
+    }
+}
+__global__ void __launch_bounds__(256) ema_step_scalar_kernel(float* __restrict__ e, const float* __restrict__ w,
+                                                              bf16_t* __restrict__ shadow, size_t n, float d, float omd,
+                                                              const float* __restrict__ skip) {
+    if (skip && *skip != 0.f) return;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const float r = ema_one(e[i], w[i], d, omd);
+        e[i] = r;
+        if (shadow) shadow[i] = f2bf(r);
+    }
+}
+
+// grids of the 16-byte and the one-element-per-thread kernels (optimizer forms and EMA alike)
+static unsigned optim_vec_grid(long long n) {
+    size_t grid = ((size_t)n / 8 + 255) / 256;
+    if (grid > 256 * 8) grid = 256 * 8;
+    return (unsigned)(grid < 1 ? 1 : grid);
+}
+static unsigned optim_scalar_grid(long long n) {
+    size_t grid = ((size_t)n + 255) / 256;
+    return (unsigned)(grid > 256 * 16 ? 256 * 16 : grid);
 }
 
 extern "C" int nkb_optim_step(int kind, float* p, const float* g, float* m, float* v, void* shadow_bf16, long long n,
                               float lr, float wd, float beta1, float beta2, float eps, float grad_scale, float c0,
                               float c1, float c2, float c3, const float* skip_flag, hipStream_t stream) {
-    if (kind < 0 || kind > 3) { nkb_set_error("optim_step: kind %d is none of 0 adam, 1 nadam, 2 radam, 3 sgd", kind); return 1; }
+    if (kind == NKB_OPTIM_EMA) {           // p: the EMA range, g: the model's master weights, beta1 = d, beta2 = 1 - d
+        if (n <= 0) return 0;
+        NkbProfScope prof(NKB_K_OPTIM, stream, 0, (shadow_bf16 ? 14.0 : 12.0) * n);
+        const bool aligned = (((uintptr_t)p | (uintptr_t)g) & 15) == 0 && ((uintptr_t)shadow_bf16 & 7) == 0;
+        if (aligned)
+            hipLaunchKernelGGL(ema_step_kernel, dim3(optim_vec_grid(n)), dim3(256), 0, stream, p, g, (bf16_t*)shadow_bf16,
+                               (size_t)n, beta1, beta2, skip_flag);
+        else
+            hipLaunchKernelGGL(ema_step_scalar_kernel, dim3(optim_scalar_grid(n)), dim3(256), 0, stream, p, g,
+                               (bf16_t*)shadow_bf16, (size_t)n, beta1, beta2, skip_flag);
+        return nkb_check_launch("optim_step");
+    }
+    const int clip_bits = kind & (NKB_OPTIM_CLIP_NORM | NKB_OPTIM_CLIP_VALUE);
+    if (kind < 0 || (kind & ~clip_bits) > 3) {
+        nkb_set_error("optim_step: kind %d is none of 0 adam, 1 nadam, 2 radam, 3 sgd", kind);
+        return 1;
+    }
+    if (clip_bits == (NKB_OPTIM_CLIP_NORM | NKB_OPTIM_CLIP_VALUE)) {
+        nkb_set_error("optim_step: kind %d asks for both clip forms (NKB_OPTIM_CLIP_NORM | NKB_OPTIM_CLIP_VALUE); one at a time", kind);
+        return 1;
+    }
+    if (clip_bits && !skip_flag) {
+        nkb_set_error("optim_step: kind %d clips the gradient and needs the device record {skip, bound, P, 0, partials} in "
+                      "skip_flag, which is NULL", kind);
+        return 1;
+    }
+    kind &= 15;
     const int mode = optim_mode(kind, beta1, c0);
     if (kind == 3 && c1 != 0.f && mode != OPTIM_SGD_MOMENTUM) {
         nkb_set_error("optim_step: Nesterov SGD (c1 != 0) needs a momentum (beta1 != 0) and c0 != 0");
@@ -164,17 +287,23 @@ extern "C" int nkb_optim_step(int kind, float* p, const float* g, float* m, floa
     a.c0 = c0; a.c1 = c1; a.c2 = c2; a.c3 = c3;
     NkbProfScope prof(NKB_K_OPTIM, stream, 0);
     const bool aligned = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0 && ((uintptr_t)shadow_bf16 & 7) == 0;
+    bf16_t* sh = (bf16_t*)shadow_bf16;
     if (aligned) {
-        size_t grid = ((size_t)n / 8 + 255) / 256;
-        if (grid > 256 * 8) grid = 256 * 8;
-        if (grid < 1) grid = 1;
-        hipLaunchKernelGGL(optim_step_kernel, dim3((unsigned)grid), dim3(256), 0, stream, p, g, m, v, (bf16_t*)shadow_bf16,
-                           (size_t)n, a, skip_flag);
+        const dim3 grid(optim_vec_grid(n));
+        if (clip_bits == NKB_OPTIM_CLIP_NORM)
+            hipLaunchKernelGGL(optim_step_kernel<CLIP_NORM>, grid, dim3(256), 0, stream, p, g, m, v, sh, (size_t)n, a, skip_flag);
+        else if (clip_bits == NKB_OPTIM_CLIP_VALUE)
+            hipLaunchKernelGGL(optim_step_kernel<CLIP_VALUE>, grid, dim3(256), 0, stream, p, g, m, v, sh, (size_t)n, a, skip_flag);
+        else
+            hipLaunchKernelGGL(optim_step_kernel<CLIP_NONE>, grid, dim3(256), 0, stream, p, g, m, v, sh, (size_t)n, a, skip_flag);
     } else {
-        size_t grid = ((size_t)n + 255) / 256;
-        if (grid > 256 * 16) grid = 256 * 16;
-        hipLaunchKernelGGL(optim_step_scalar_kernel, dim3((unsigned)grid), dim3(256), 0, stream, p, g, m, v, (bf16_t*)shadow_bf16,
-                           (size_t)n, a, skip_flag);
+        const dim3 grid(optim_scalar_grid(n));
+        if (clip_bits == NKB_OPTIM_CLIP_NORM)
+            hipLaunchKernelGGL(optim_step_scalar_kernel<CLIP_NORM>, grid, dim3(256), 0, stream, p, g, m, v, sh, (size_t)n, a, skip_flag);
+        else if (clip_bits == NKB_OPTIM_CLIP_VALUE)
+            hipLaunchKernelGGL(optim_step_scalar_kernel<CLIP_VALUE>, grid, dim3(256), 0, stream, p, g, m, v, sh, (size_t)n, a, skip_flag);
+        else
+            hipLaunchKernelGGL(optim_step_scalar_kernel<CLIP_NONE>, grid, dim3(256), 0, stream, p, g, m, v, sh, (size_t)n, a, skip_flag);
     }
     return nkb_check_launch("optim_step");
 }
@@ -185,8 +314,24 @@ __global__ void seg_sumsq_kernel(const float* __restrict__ x, const long long* _
     const int k = blockIdx.x;
     if (k >= nseg) return;
     __shared__ float s[4];
+    const long long lo = offsets[k], hi = offsets[k + 1];
     float t = 0.f;
-    for (long long i = offsets[k] + threadIdx.x; i < offsets[k + 1]; i += blockDim.x) t += x[i] * x[i];
+    if (hi > lo && ((uintptr_t)(x + lo) & 15) == 0) {
+        // a segment that starts on 16 bytes (the equal chunks of the clip-norm pass, 4 B per parameter): 16-byte loads, one
+        // accumulator per vector lane; the order differs from the scalar loop's, the result is the same bits from run to run
+        const long long n4 = (hi - lo) >> 2;
+        const f32x4* x4 = (const f32x4*)(x + lo);
+        float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
+#pragma unroll 2
+        for (long long i = threadIdx.x; i < n4; i += blockDim.x) {
+            const f32x4 q = x4[i];
+            t0 += q[0] * q[0]; t1 += q[1] * q[1]; t2 += q[2] * q[2]; t3 += q[3] * q[3];
+        }
+        t = (t0 + t1) + (t2 + t3);
+        for (long long i = lo + (n4 << 2) + threadIdx.x; i < hi; i += blockDim.x) t += x[i] * x[i];
+    } else {
+        for (long long i = lo + threadIdx.x; i < hi; i += blockDim.x) t += x[i] * x[i];
+    }
     t = wave_sum(t);
     if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = t;
     __syncthreads();

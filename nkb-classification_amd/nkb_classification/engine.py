@@ -19,6 +19,7 @@ from tqdm import tqdm
 
 from . import hip
 from .losses import MixedTarget
+from .utils import parse_clip_grad
 
 
 class TrainPbar(tqdm):
@@ -97,11 +98,31 @@ def _forward_and_loss(model, criterion, img, target, device, cfg):
         return preds, labels, criterion(preds, labels)
 
 
+def _clip_gradients(optimizer, scaler, clip, grad_log):
+    """cfg.clip_grad between backward and the step, in torch's order: unscale first, then arm the optimizer's clip (the
+    coefficient is derived and applied on the device, inside the step's launches)."""
+    mode, bound = clip
+    if not hasattr(optimizer, "clip_grad_norm_"):
+        raise NotImplementedError(f"cfg.clip_grad needs the fused optimizer (clipping runs inside nkb_optim_step), "
+                                  f"not {type(optimizer).__name__}")
+    scaler.unscale_(optimizer)
+    if mode == "value":
+        optimizer.clip_grad_value_(bound)
+        return
+    norm = optimizer.clip_grad_norm_(bound, return_norm=grad_log is not None)
+    if grad_log is not None:
+        grad_log["Gradients/ClipNorm"].append(norm)
+
+
 def train_epoch(model, train_loader, optimizer, scheduler, scaler, criterion, device, cfg, epoch_logger):
-    """One training epoch (engine.py:20-85), positional arguments in the reference's order."""
+    """One training epoch (engine.py:20-85), positional arguments in the reference's order.  Optional beyond the reference:
+    `cfg.clip_grad` ({"max_norm": x} / {"clip_value": x}) clips between backward and the step, and a `model.ema`
+    (ema.ModelEma) is advanced after every step."""
     model.train()
     epoch_logger.init_iter_logs()
     grad_log = defaultdict(list) if cfg.log_gradients else None
+    clip = parse_clip_grad(getattr(cfg, "clip_grad", None))
+    ema = getattr(model, "ema", None)
     bar = TrainPbar(train_loader, leave=False, desc="Training", cfg=cfg)
     for img, target in bar:
         img = img.to(device, non_blocking=True)
@@ -110,8 +131,12 @@ def train_epoch(model, train_loader, optimizer, scheduler, scaler, criterion, de
         bar.update_loss(loss)                              # prints the previous step's loss: no sync between fwd and bwd
         total = loss["loss"] if isinstance(loss, dict) else loss
         scaler.scale(total).backward()
+        if clip is not None:
+            _clip_gradients(optimizer, scaler, clip, grad_log)
         scaler.step(optimizer)
         scaler.update()
+        if ema is not None:
+            ema.update()
         epoch_logger.log_iter(preds, _primary(_upload(target, device) if isinstance(target, dict) else target), loss)
         if grad_log is not None:
             _grad_norms(model, grad_log)

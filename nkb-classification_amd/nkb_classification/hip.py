@@ -773,10 +773,41 @@ def loss_backward(probs, ldp, target, row_state, out2, grad_out, B, C_, dlogits,
                                    C_, ptr(dlogits), ldd, stream()), "loss_backward")
 
 
+# NKB_OPTIM_* of nkbhip.h: kind | 16 / kind | 64 clip the gradient inside the launch (skip_flag is then the device record
+# {skip, bound, P, 0, partials[P]}), kind == 32 is the weight-EMA form
+OPTIM_CLIP_NORM, OPTIM_CLIP_VALUE, OPTIM_EMA = 16, 64, 32
+OPTIM_MAX_PARTIALS = 4096           # most partial sums of squares a clip-norm record may carry
+OPTIM_RECORD_HEAD = 4               # words of the record in front of the partials
+
+
+def clip_chunks(total: int):
+    """(chunk length, P): the gradient arena cut into P equal chunks for the clip-norm pass (nkb_segment_sumsq, one workgroup per
+    chunk).  At least 16384 elements per chunk, a multiple of 4 (every chunk starts on 16 bytes), and P <= 4096."""
+    if total < 1:
+        raise ValueError(f"clip_chunks: total must be positive, got {total}")
+    per = -(-total // OPTIM_MAX_PARTIALS)
+    chunk = max(16384, (per + 3) // 4 * 4)
+    return chunk, -(-total // chunk)
+
+
+def clip_chunk_offsets(total: int):
+    """The P + 1 segment offsets of clip_chunks(total): they tile [0, total) exactly (host list; the caller uploads it once)."""
+    chunk, P = clip_chunks(total)
+    return [min(k * chunk, total) for k in range(P + 1)]
+
+
 def optim_step(kind, p, g, m, v, shadow, n, lr, wd, beta1, beta2, eps, grad_scale, c0=0.0, c1=0.0, c2=0.0, c3=0.0,
                skip_flag=None):
+    """kind | OPTIM_CLIP_NORM / OPTIM_CLIP_VALUE: skip_flag is the clip record; kind == OPTIM_EMA: see ema_step"""
     check(load().nkb_optim_step(kind, ptr(p), ptr(g), ptr(m), ptr(v), ptr(shadow), n, lr, wd, beta1, beta2, eps,
                                 grad_scale, c0, c1, c2, c3, ptr(skip_flag), stream()), "optim_step")
+
+
+def ema_step(ema, weights, shadow, n, decay, skip_flag=None):
+    """ema = (d * ema) + ((1 - d) * weights) over n fp32 elements (nkb_optim_step, kind NKB_OPTIM_EMA); 1 - d is subtracted in
+    double here and rounded to fp32 once, by the call"""
+    d = float(decay)
+    optim_step(OPTIM_EMA, ema, weights, None, None, shadow, n, 0.0, 0.0, d, 1.0 - d, 0.0, 1.0, skip_flag=skip_flag)
 
 
 def bucket_sum_bf16(parts, stride, nparts, out, out_bf16, n):

@@ -6,7 +6,7 @@ families, but the update itself is one fused HIP launch per group over the model
 (nkb_optim_step) instead of torch's foreach kernels.  Beyond the reference: `type: "adamw"`, the optional keys
 `betas`, `eps`, `momentum`, `dampening`, `nesterov`, `decoupled_weight_decay`, `amsgrad` (refused when true) and
 `layer_decay` (one backbone group per transformer block); a config without them builds what the reference builds.
-`get_scheduler` (utils.py:45-61) returns the stock
+`parse_clip_grad` reads the optional `cfg.clip_grad`.  `get_scheduler` (utils.py:45-61) returns the stock
 torch schedulers, which only touch `param_groups[i]["lr"]` on the host.
 """
 from __future__ import annotations
@@ -77,6 +77,7 @@ class FusedOptimizer(torch.optim.Optimizer):
     When every parameter of a group is a view into the model's flat arena (see model.ParamArena) the group is
     updated by ONE launch over the contiguous range, which also refreshes the bf16 shadow weights; otherwise
     each parameter gets its own launch.  `grad_scale` (e.g. 1/world_size) is folded into the kernel.
+    `clip_grad_norm_` / `clip_grad_value_` arm the next step(): its launches clip the gradients as they read them.
     """
 
     def __init__(self, params, kind: str, arena=None, **options):
@@ -129,6 +130,85 @@ class FusedOptimizer(torch.optim.Optimizer):
 
     _prev_gstate = None
 
+    # ---- gradient clipping, decided on the device (nkbhip.h: NKB_OPTIM_CLIP_NORM / NKB_OPTIM_CLIP_VALUE) ------------------------
+    # torch's idiom `scaler.unscale_(opt); clip_grad_norm_(params); scaler.step(opt)` keeps its place and order, but nothing is
+    # scaled between backward and step: the clip methods ARM the next step(), whose launches derive the coefficient from a device
+    # record and apply it to each gradient as they read it.  The gradient arena itself stays as backward left it.
+    _clip = None              # kind bit of the armed form, cleared by step()
+    _clip_rec = None          # device record {skip, bound, P, 0, partials[P]}
+    _clip_offsets = None      # int64 device offsets of the P chunks of flat_grad (built once per arena)
+    _clip_P = 0
+    _clip_bound = None        # host copy of rec[1]
+    _clip_rec0_set = False    # rec[0] may hold a scaler's flag from an earlier step
+
+    def _clip_arena(self, what: str):
+        a = self.arena
+        if a is None or not a.packed or not all(a.owns(p) for g in self.param_groups for p in g["params"]):
+            raise NotImplementedError(f"{what} clips inside the fused launches over the packed parameter arena and needs every "
+                                      "parameter of every group to live there; there is no torch fallback "
+                                      "(torch.nn.utils.clip_grad_norm_ would read the norm back on the host)")
+        if self._clip_rec is None or self._clip_rec.device != a.flat_grad.device or self._clip_total != a.total:
+            offs = hip.clip_chunk_offsets(a.total)
+            self._clip_P, self._clip_total = len(offs) - 1, a.total
+            self._clip_offsets = torch.tensor(offs, dtype=torch.int64, device=a.flat_grad.device)
+            self._clip_rec = torch.zeros(hip.OPTIM_RECORD_HEAD + self._clip_P, dtype=torch.float32, device=a.flat_grad.device)
+            self._clip_rec[2].fill_(float(self._clip_P))
+            self._clip_bound, self._clip_rec0_set = None, False
+        return a
+
+    _clip_total = -1
+
+    def _clip_set_bound(self, bound: float):
+        if self._clip_bound != bound:                   # a device-side fill: the bound changes once per run, if at all
+            self._clip_rec[1].fill_(bound)
+            self._clip_bound = bound
+
+    @torch.no_grad()
+    def clip_grad_norm_(self, max_norm, return_norm=False):
+        """torch.nn.utils.clip_grad_norm_(parameters, max_norm) (norm_type 2) for the NEXT step(): one nkb_segment_sumsq pass over the
+        gradient arena leaves partial sums of squares in the device record, and every launch of the step scales the gradients it
+        reads by min(1, max_norm / (norm + 1e-6)).  Call it after backward (and after scaler.unscale_).  return_norm=True returns the
+        total norm as a device scalar; nothing waits for the device."""
+        max_norm = float(max_norm)
+        if not max_norm >= 0.0:
+            raise ValueError(f"Invalid max_norm value: {max_norm}")
+        a = self._clip_arena("clip_grad_norm_")
+        with torch.cuda.device(a.flat_grad.device):
+            self._clip_set_bound(max_norm)
+            rec = self._clip_rec
+            hip.segment_sumsq(a.flat_grad, self._clip_offsets, self._clip_P, rec[hip.OPTIM_RECORD_HEAD:])
+            self._clip = hip.OPTIM_CLIP_NORM
+            if return_norm:
+                return rec[hip.OPTIM_RECORD_HEAD:].sum().sqrt() * abs(float(self.grad_scale))
+        return None
+
+    @torch.no_grad()
+    def clip_grad_value_(self, clip_value):
+        """torch.nn.utils.clip_grad_value_(parameters, clip_value) for the NEXT step(): its launches clamp each (averaged) gradient
+        to [-clip_value, clip_value] as they read it."""
+        clip_value = float(clip_value)
+        if not clip_value >= 0.0:
+            raise ValueError(f"Invalid clip_value value: {clip_value}")
+        a = self._clip_arena("clip_grad_value_")
+        with torch.cuda.device(a.flat_grad.device):
+            self._clip_set_bound(clip_value)
+        self._clip = hip.OPTIM_CLIP_VALUE
+
+    def _clip_launch_args(self, skip_flag):
+        """(kind bits, skip_flag) of this step's launches: an armed clip hands them the record, with the scaler's flag (one float,
+        copied device to device on the stream) or 0 in its first word."""
+        bits, self._clip = self._clip, None
+        if bits is None:
+            return 0, skip_flag
+        rec = self._clip_rec
+        if skip_flag is not None:
+            rec[0:1].copy_(skip_flag.reshape(-1)[0:1], non_blocking=True)
+            self._clip_rec0_set = True
+        elif self._clip_rec0_set:
+            rec[0:1].zero_()
+            self._clip_rec0_set = False
+        return bits, rec
+
     @torch.no_grad()
     def step(self, closure=None, skip_flag=None):
         """skip_flag: device float; when it is non-zero at execution time the launches of this step do nothing."""
@@ -144,6 +224,7 @@ class FusedOptimizer(torch.optim.Optimizer):
         return self._step_impl(loss, skip_flag)
 
     def _step_impl(self, loss, skip_flag):
+        clip_bits, skip_flag = self._clip_launch_args(skip_flag)
         touched_arena = False
         shadowed = 0            # arena elements whose bf16 shadow this step's launches rewrote
         for group, gstate in zip(self.param_groups, self._gstate):
@@ -169,7 +250,7 @@ class FusedOptimizer(torch.optim.Optimizer):
                 m, v = a.moments()
                 shadow = a.shadow[lo:hi] if a.shadow is not None else None
                 # (SGD with momentum keeps its buffer in the first moment and never reads the second)
-                hip.optim_step(kcode, a.flat_param[lo:hi], a.flat_grad[lo:hi], m[lo:hi], None if momentum else v[lo:hi], shadow, hi - lo,
+                hip.optim_step(kcode | clip_bits, a.flat_param[lo:hi], a.flat_grad[lo:hi], m[lo:hi], None if momentum else v[lo:hi], shadow, hi - lo,
                                lr, wd, beta1, beta2, eps, self.grad_scale, *sc, skip_flag=skip_flag)
                 touched_arena = True
                 if shadow is not None and len(live) == len(group["params"]):
@@ -192,7 +273,7 @@ class FusedOptimizer(torch.optim.Optimizer):
                     raise RuntimeError("FusedOptimizer: parameters and gradients must be fp32")
                 if not (_dense(p) and _dense(g) and p.stride() == g.stride()):
                     raise RuntimeError("FusedOptimizer: parameter/gradient must be dense with equal strides")
-                hip.optim_step(kcode, p, g, st.get("momentum_buffer") if sgd else st.get("exp_avg"), st.get("exp_avg_sq"), None,
+                hip.optim_step(kcode | clip_bits, p, g, st.get("momentum_buffer") if sgd else st.get("exp_avg"), st.get("exp_avg_sq"), None,
                                p.numel(), lr, wd, beta1, beta2, eps, self.grad_scale, *psc, skip_flag=skip_flag)
                 if self.arena is not None and self.arena.owns(p):
                     touched_arena = True
@@ -231,6 +312,38 @@ def _validate(kind: str, group: dict):
                                   "has no pointer for one")
     if kind == "nadam" and not group.get("decoupled_weight_decay", True):
         raise NotImplementedError("nadam runs with decoupled weight decay only, as the reference builds it")
+
+
+def parse_clip_grad(spec):
+    """cfg.clip_grad -> None or ("norm" | "value", bound).  {"max_norm": 1.0} and {"clip_value": 0.5} are torch's names;
+    {"mode": "norm" | "value", "clip_grad": x} timm's (its `clip_mode` / `clip_grad`; "agc" is not implemented)."""
+    if spec is None:
+        return None
+    if not isinstance(spec, dict):
+        raise ValueError(f"clip_grad must be a dict such as {{'max_norm': 1.0}} or {{'clip_value': 0.5}}, got {spec!r}")
+    unknown = set(spec) - {"max_norm", "clip_value", "mode", "clip_grad"}
+    if unknown:
+        raise ValueError(f"clip_grad: unknown keys {sorted(unknown)}")
+    given = [k for k in ("max_norm", "clip_value", "clip_grad") if k in spec]
+    if len(given) != 1:
+        raise ValueError(f"clip_grad needs exactly one of max_norm, clip_value or (with mode) clip_grad, got {sorted(spec)}")
+    key = given[0]
+    mode = spec.get("mode")
+    if mode is not None and mode not in ("norm", "value"):
+        raise ValueError(f"clip_grad: mode must be 'norm' or 'value', got {mode!r}"
+                         + (" (adaptive gradient clipping is not implemented)" if mode == "agc" else ""))
+    if key == "clip_grad":
+        if mode is None:
+            raise ValueError("clip_grad: the key clip_grad needs a mode ('norm' or 'value')")
+    else:
+        implied = "norm" if key == "max_norm" else "value"
+        if mode is not None and mode != implied:
+            raise ValueError(f"clip_grad: mode {mode!r} contradicts the key {key}")
+        mode = implied
+    bound = float(spec[key])
+    if not bound >= 0.0:
+        raise ValueError(f"Invalid {'max_norm' if mode == 'norm' else 'clip_value'} value: {bound}")
+    return mode, bound
 
 
 def _dense(t: torch.Tensor) -> bool:

@@ -17,6 +17,7 @@ Environment (tests / rehearsals): NKB_DDP_BACKEND (default "nccl" = RCCL), NKB_D
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 import sys
 from pathlib import Path
@@ -30,6 +31,7 @@ from tqdm import tqdm  # noqa: E402
 sys.path.insert(0, str(Path(__file__).resolve().parent))
 
 from nkb_classification.dataset import get_dataset  # noqa: E402
+from nkb_classification.ema import ModelEma  # noqa: E402
 from nkb_classification.engine import train_epoch, val_epoch  # noqa: E402
 from nkb_classification.logging import TrainLogger, get_local_experiment  # noqa: E402
 from nkb_classification.losses import get_loss  # noqa: E402
@@ -64,8 +66,10 @@ def train(model, train_loader, val_loader, optimizer, scheduler, criterion, come
             train_epoch(model, train_loader, optimizer, scheduler, scaler, criterion, device, cfg, train_logger),
             real_len=_real_len(train_loader))
         scaler.settle()          # a skipped LAST step must not stay counted in the optimizer state the checkpoint sees
-        val_results = parallel.gather_epoch_results(val_epoch(model, val_loader, criterion, device, cfg, train_logger),
-                                                    real_len=_real_len(val_loader))
+        ema = getattr(model, "ema", None)      # cfg.model_ema: validate, and keep as best, the averaged weights
+        with ema.applied() if ema is not None else contextlib.nullcontext():
+            val_results = parallel.gather_epoch_results(val_epoch(model, val_loader, criterion, device, cfg, train_logger),
+                                                        real_len=_real_len(val_loader))
         train_results["metrics"] = compute_metrics(cfg, train_results)
         val_results["metrics"] = compute_metrics(cfg, val_results)
         epoch_val_acc = val_results["metrics"]["epoch_acc"]
@@ -74,10 +78,13 @@ def train(model, train_loader, val_loader, optimizer, scheduler, criterion, come
             continue
         if epoch_val_acc is not None and epoch_val_acc > best_val_acc:
             best_val_acc = epoch_val_acc
-            torch.save(model.state_dict(), Path(model_path, "best.pth"))
-            save_scripted(model, Path(model_path, "scripted_best.pt"))
-        torch.save(model.state_dict(), Path(model_path, "last.pth"))
+            with ema.applied() if ema is not None else contextlib.nullcontext():     # the weights that were validated
+                torch.save(model.state_dict(), Path(model_path, "best.pth"))
+                save_scripted(model, Path(model_path, "scripted_best.pt"))
+        torch.save(model.state_dict(), Path(model_path, "last.pth"))      # the raw weights: what training resumes from
         save_scripted(model, Path(model_path, "scripted_last.pt"))
+        if ema is not None:
+            torch.save(ema.state_dict(), Path(model_path, "ema_last.pth"))
     return train_results, val_results
 
 
@@ -121,6 +128,9 @@ def main():
     if world > 1:
         parallel.attach(model, optimizer, device)
         torch.manual_seed(seed + 1 + rank)     # dropout / stochastic-depth draws differ per rank from here on
+    if getattr(cfg, "model_ema", None) is not None:  # noqa: F821
+        # after the broadcast of parallel.attach: every rank averages its own, identical copy (no communication)
+        model.ema = ModelEma(model, **cfg.model_ema)  # noqa: F821
     # train.py:104-108: only rank 0 owns the run directory (no exists()->mkdir race, one metrics.csv)
     local_experiment = get_local_experiment(cfg.experiment["local"]) if rank == 0 else None  # noqa: F821
     out = train(model, train_loader, val_loader, optimizer, scheduler, criterion, None, local_experiment, device, cfg)  # noqa: F821
